@@ -14,6 +14,11 @@ ranks by one RCCL broadcast per replan (the only exchange the path has).
                                                    every map with a patch stream of its own
   python bench.py --size 8192 --seed 42 --heuristic                          config 5 (this GPU's replica)
 
+A plain run sets up, warms up, times the --steps episodes and prints the line.  `--full` adds what takes work of its
+own: at N = 1 the second leg with the patches resident in HBM (`value_device_inputs`), the CPU baseline, and the
+self-check of every rank's raster against map + patches.  `--dump-outputs DIR` writes what the last timed episode
+computed (dump_outputs below) as DIR/<name>.npy.
+
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment: this process starts N rank processes (fresh
 interpreters, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set) before anything touches a GPU, watches all of
 them -- the first one to fail ends the others within seconds, its stderr tail is relayed and its exit code is
@@ -49,6 +54,70 @@ ALGO_LABEL = {"FD": "Field D* level-1", "SG": "Shifted-Grid FM level-2", "DFM": 
 
 def opt_level(algo_name):
     return 2 if algo_name == "SG" else 1
+
+
+# ---------------------------------------------------------------------------------------------------------
+# --dump-outputs: what a caller of the timed path receives after its last step -- the field (G, RHS) and the
+# path extracted from the robot's last position -- so that two builds can be compared output for output.
+# The whole field is written as a fixed, seeded sample (the same positions in every run with the same
+# arguments) of its finalised part (below_start_key), next to a dense window around the start, where the
+# path is read.  Every value written is finite: an element without a value (G = RHS = +inf: unreached, or an
+# obstacle) or, in the samples, one not finalised is written as DUMP_NO_VALUE, which no cost-to-goal takes.
+# ---------------------------------------------------------------------------------------------------------
+DUMP_SAMPLE = 1 << 20           # values per sampled field (4 MB in float32)
+DUMP_NO_VALUE = -1.0
+DUMP_WINDOW = 64                # edge of the dense window around the start
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_sample(a, n, seed=0):
+    flat = np.ascontiguousarray(a).reshape(-1)
+    if flat.size <= n:
+        return flat.copy()
+    return flat[np.sort(np.random.default_rng(seed).choice(flat.size, n, replace=False))]
+
+
+def below_start_key(g, xy, nodes):
+    """mask of the elements a step has finalised: G below the start's key (the largest finite G of the start cell's
+    corner nodes, or of the start cell).  Beyond it a focused step stops (end_condition), and what is left there
+    differs from run to run."""
+    x, y = int(xy[0]), int(xy[1])
+    around = g[x:x + 2, y:y + 2] if nodes else g[x:x + 1, y:y + 1]
+    fin = around[np.isfinite(around)]
+    return g < (fin.max() if fin.size else -np.inf)
+
+
+def with_values(a, mask=None):
+    """`a` with DUMP_NO_VALUE where it is not finite (or outside `mask`)"""
+    keep = np.isfinite(a) if mask is None else (np.isfinite(a) & mask)
+    return np.where(keep, a, a.dtype.type(DUMP_NO_VALUE))
+
+
+def final_sample(a, mask, n, seed=0):
+    return dump_sample(with_values(a, mask), n, seed)
+
+
+def dump_window(a, xy, edge=DUMP_WINDOW):
+    x0 = min(max(0, int(xy[0]) - edge // 2), max(0, a.shape[0] - edge))
+    y0 = min(max(0, int(xy[1]) - edge // 2), max(0, a.shape[1] - edge))
+    return with_values(np.ascontiguousarray(a[x0:x0 + edge, y0:y0 + edge]))
+
+
+def path_arrays(prefix, path):
+    pts, costs, total_cost, total_dist = path
+    return {prefix + "path_points": with_values(np.asarray(pts, np.float32)), prefix + "path_step_costs": with_values(np.asarray(costs, np.float32)),
+            prefix + "path_total": with_values(np.array([total_cost, total_dist], np.float64))}
+
+
+def dump_outputs(dirpath, arrays):
+    arrays = {k: (v if v.dtype in (np.float32, np.float64) else v.astype(np.float64)) for k, v in arrays.items()}
+    assert all(np.isfinite(v).all() for v in arrays.values())
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes, more than the %d allowed" % (total, DUMP_MAX_BYTES))
+    os.makedirs(dirpath, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(dirpath, name + ".npy"), v)
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -386,6 +455,15 @@ def run_rank(args, planner_factory=None, factory_label=None):
             for (_k, _s, top, left, patch) in script:
                 expect[top:top + patch.shape[0], left:left + patch.shape[1]] = patch
             return [(0, planner.read_map(size, size), expect)]
+
+        def last_outputs():
+            pos = script[-1][1] if script else start
+            g, rhs = planner.read_field()
+            fin = below_start_key(g, pos, args.algo != "DFM")
+            out = {"g_sample": final_sample(g, fin, DUMP_SAMPLE), "rhs_sample": final_sample(rhs, fin, DUMP_SAMPLE),
+                   "g_near_start": dump_window(g, pos), "rhs_near_start": dump_window(rhs, pos)}
+            out.update(path_arrays("", planner.extract_path(max_steps=20, allow_indirect=args.algo != "SG")))
+            return out
         n_rounds = len(script)
     else:
         # ---- M independent maps per rank, every map with its own patch stream (config 4) ----
@@ -468,6 +546,16 @@ def run_rank(args, planner_factory=None, factory_label=None):
                 out.append((m, planner.read_map(m, size, size), expect))
             return out
 
+        def last_outputs():
+            pos = starts[-1] if starts else start
+            out = {}
+            for m, path in enumerate(planner.extract_paths(max_steps=20, allow_indirect=args.algo != "SG")):
+                g = planner.read_field(m)
+                out["map%d_g_sample" % m] = final_sample(g, below_start_key(g, pos, args.algo != "DFM"), max(1, DUMP_SAMPLE // M), seed=m)
+                out["map%d_g_near_start" % m] = dump_window(g, pos)
+                out.update(path_arrays("map%d_" % m, path))
+            return out
+
     phases = {}         # host wall seconds of the episodes' parts, summed over warm-up and timed episodes (run_episode)
     if M != 0:
         legs, leg = {"device": None}, ["device"]
@@ -487,6 +575,8 @@ def run_rank(args, planner_factory=None, factory_label=None):
     for _ in range(args.warmup):
         run_warm()
     dt, per_step = ep.timed_episodes(run_one, args.steps, 0, barrier)
+    if args.dump_outputs and rank == 0:        # (before a second leg: what the timed episodes of `value` computed)
+        dump_outputs(args.dump_outputs, last_outputs())
     device_leg = None
     if leg[0] == "host" and args.patch_inputs == "both":            # the second leg: the same episodes with the patches resident in HBM (ufm_patch_map_device)
         phases_host = dict(phases)
@@ -515,8 +605,8 @@ def run_rank(args, planner_factory=None, factory_label=None):
     res = [sum(d.get(k, 0) for d in per_step) for k in ("res_visits", "res_launches", "res_kernel_ms")]
     reg = [sum(d.get(k, 0) for d in per_step) for k in ("reg_launches", "reg_timed", "reg_kernel_ms", "reg_tiles", "reg_cells")]
 
-    # self-check of the patch path (outside the timed region)
-    for m, got, expect in self_check():
+    # self-check of the patch path (outside the timed region; --full)
+    for m, got, expect in (self_check() if args.full else []):
         if not np.array_equal(got, expect):
             bad = np.argwhere(got != expect)
             raise RuntimeError("rank %d map %d: raster on the device differs from map + patches in %d cells, first at %r (device %d, expected %d)" % (
@@ -649,7 +739,7 @@ def run_rank(args, planner_factory=None, factory_label=None):
                 "kernel_time_share": avg_s * rl_ / dt,
                 "note": "one CU of 256: a replan changes ~1 k elements; latency-bound chain of dependent patch sweeps (DESIGN.md 4.6)",
             }
-        if not rehearsal and not args.no_cpu_baseline and world == 1:   # the CPU baseline is reported at N = 1 only
+        if not rehearsal and args.full and not args.no_cpu_baseline and world == 1:   # the CPU baseline is reported at N = 1 only
             out["cpu_baseline"] = cpu_baseline(args.cpu_size, seed, n_rounds, args.algo, bool(args.heuristic), n_local)
         print(json.dumps(out))
     stream.close()
@@ -678,7 +768,11 @@ def main(argv=None, planner_factory=None, factory_label=None, script=None):
                     "stream (BASELINE config 4: --gpus 8 --algo DFM --size 2048 --batch 8)")
     ap.add_argument("--heuristic", action="store_true",
                     help="heuristic keys with hm = the map's smallest cost (planners built without -DNO_HEURISTIC; BASELINE config 5 with --size 8192)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the HBM-resident patch leg (N = 1), the CPU baseline and the rasters' self-check")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed episode computed (field sample, window around the start, path) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-size", type=int, default=None, help="map size of the CPU baseline sample (default: the identical workload)")
     ap.add_argument("--no-profile", action="store_true", help="skip per-launch HIP event timing")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
@@ -690,15 +784,20 @@ def main(argv=None, planner_factory=None, factory_label=None, script=None):
     ap.add_argument("--timeout", type=float, default=1500.0, help="--gpus N self-launch: seconds after which the rank processes are stopped (exit code 124)")
     ap.add_argument("--param", action="append", default=[], metavar="NAME=VALUE",
                     help="scheduler knob for the engine (ufm_set_param / ufm_batch_set_param), e.g. owned_waves=16; for experiments -- the defaults are the product")
-    ap.add_argument("--patch-inputs", default="both", choices=["both", "host", "device"],
-                    help="N = 1, one map per GPU: where the patches come from.  both (default): the episodes with patches from host memory are `value`, a second leg "
-                    "with the patches resident in HBM is `value_device_inputs`; host / device: that leg only (profiles).  With a process group the patches arrive in HBM")
+    ap.add_argument("--patch-inputs", default=None, choices=["both", "host", "device"],
+                    help="N = 1, one map per GPU: where the patches come from.  both (default with --full): the episodes with patches from host memory are `value`, a second leg "
+                    "with the patches resident in HBM is `value_device_inputs`; host (default without --full) / device: that leg only (profiles).  With a process group "
+                    "the patches arrive in HBM")
     ap.add_argument("--traffic-json", default="r4_traffic.json", help="file under profiles/ holding the separately collected PMC traffic of the headline run")
     args = ap.parse_args(argv)
     if args.seed is None:
         args.seed = 1000 if args.batch > 0 else 7
     if args.cpu_size is None:
         args.cpu_size = args.size
+    if args.patch_inputs is None:
+        args.patch_inputs = "both" if args.full else "host"
+    if args.dump_outputs and planner_factory is not None:
+        raise SystemExit("--dump-outputs: the stand-in planner of a rehearsal has no field to write")
     if args.gpus < 1 or args.batch < 0:
         raise SystemExit("--gpus >= 1, --batch >= 0")
     env_world = os.environ.get("WORLD_SIZE")

@@ -1,6 +1,6 @@
 """-m gpu: bench.py's output contract on a small instance of the headline workload (the driver runs the
-full-size one): one JSON line with the metric, the roofline object of the dominant kernel and the CPU
-baseline, and the same line with the collectives switched on (one rank on RCCL)."""
+full-size one): one JSON line with the metric, the roofline object of the dominant kernel and (--full) the CPU
+baseline, the same line with the collectives switched on (one rank on RCCL), and a plain run's line and outputs."""
 import json
 import os
 import subprocess
@@ -26,7 +26,7 @@ def _run(*extra):
 
 
 def test_bench_line_single_gpu():
-    d = _run()
+    d = _run("--full")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in d, k
@@ -57,10 +57,10 @@ def test_bench_line_single_gpu():
 
 
 def test_bench_line_with_collectives_one_rank():
-    d = _run("--force-dist", "--no-cpu-baseline")        # RCCL: init, broadcast per replan (one ahead), all_reduce, barrier
+    d = _run("--full", "--force-dist", "--no-cpu-baseline")        # RCCL: init, broadcast per replan (one ahead), all_reduce, barrier
     assert d["n_gpus"] == 1 and d["value"] > 0
     assert d["config"]["patch_inputs"] == "device" and "value_device_inputs" not in d      # with a process group the patches arrive in HBM
-    d = _run("--force-dist", "--no-pipeline", "--no-cpu-baseline")
+    d = _run("--full", "--force-dist", "--no-pipeline", "--no-cpu-baseline")
     assert d["value"] > 0
 
 
@@ -69,7 +69,7 @@ def test_bench_self_launcher_two_ranks_on_one_gpu():
     of the box and talk over gloo (RCCL needs a device per rank), the planner is the HIP engine."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--size", "1024", "--patches", "6",
-                          "--steps", "1", "--warmup", "1"], capture_output=True, text=True, timeout=600, env=env)
+                          "--steps", "1", "--warmup", "1", "--full"], capture_output=True, text=True, timeout=600, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -81,7 +81,24 @@ def test_bench_self_launcher_two_ranks_on_one_gpu():
 def test_bench_batch_config4_shape_small():
     """config 4's shape on one GPU at a small size: --batch maps in one handle, a patch stream per map, the
     process-parallel CPU leg with the host's core count in the line"""
-    d = _run("--algo", "DFM", "--batch", "3", "--size", "512", "--cpu-size", "512", "--patches", "4")
+    d = _run("--full", "--algo", "DFM", "--batch", "3", "--size", "512", "--cpu-size", "512", "--patches", "4")
     assert d["config"]["maps_per_gpu"] == 3 and d["value"] > 0 and d["roofline"]["frac"] > 0
     c = d["cpu_baseline"]
     assert c["cores_used"] == min(3, c["cores_host"]) and c["value"] > 0
+
+
+def test_bench_plain_run_and_its_outputs(tmp_path):
+    """a plain run: the headline leg alone (no CPU baseline, no second leg), exactly --steps timed episodes; --dump-outputs writes what
+    the last one computed -- a seeded sample of the field, the window around the start, the path -- as finite float32 / float64, 64 MB at most"""
+    import numpy as np
+    import ufm_amd
+    d = _run("--steps", "2", "--dump-outputs", str(tmp_path / "out"))
+    assert d["steps"] == 2 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert "cpu_baseline" not in d and "value_device_inputs" not in d and d["config"]["patch_inputs"] == "host"
+    out = {f[:-4]: np.load(str(tmp_path / "out" / f)) for f in os.listdir(str(tmp_path / "out"))}
+    assert set(out) == {"g_sample", "rhs_sample", "g_near_start", "rhs_near_start", "path_points", "path_step_costs", "path_total"}
+    assert all(a.dtype in (np.float32, np.float64) for a in out.values()) and sum(a.nbytes for a in out.values()) <= 64 << 20
+    assert all(np.isfinite(a).all() for a in out.values())         # no value / not final: -1, which no cost-to-goal takes
+    assert out["g_sample"].shape == (1 << 20,) and out["g_near_start"].shape == (64, 64)      # 1025^2 nodes: sampled
+    last_start = list(ufm_amd.synth.replan_script(7, 1024, 1024, n_patches=6))[-1][1]
+    assert np.allclose(out["path_points"][0], last_start) and np.isfinite(out["path_total"]).all()

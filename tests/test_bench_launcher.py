@@ -16,12 +16,12 @@ import ufm_amd
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _bench(*extra, env_extra=None):
+def _bench(*extra, env_extra=None, full=True):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["PYTHONPATH"] = os.pathsep.join([os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle"), env.get("PYTHONPATH", "")])
     env.update(env_extra or {})
     out = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "bench_rehearsal.py"), "--backend", "gloo",
-                          "--steps", "1", "--warmup", "1", *extra], capture_output=True, text=True, timeout=600, env=env)
+                          "--steps", "1", "--warmup", "1", *(["--full"] if full else []), *extra], capture_output=True, text=True, timeout=600, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]
@@ -91,6 +91,15 @@ def test_the_launcher_timeout_stops_the_ranks():
 def test_one_rank_needs_no_process_group():
     d = _bench("--size", "64", "--patches", "3")
     assert d["n_gpus"] == 1 and d["config"]["broadcasts_per_rank_per_episode"] == 0
+
+
+def test_plain_run_without_full():
+    """the lean form (no self-check of the rasters): the same line; --dump-outputs needs a planner with a field"""
+    d = _bench("--gpus", "2", "--size", "64", "--patches", "3", full=False)
+    assert d["n_gpus"] == 2 and d["steps"] == 1 and d["ms_per_step"] > 0 and d["config"]["broadcasts_per_rank_per_episode"] == 3
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "bench_rehearsal.py"), "--size", "64", "--patches", "2", "--steps", "1",
+                          "--dump-outputs", "unused"], capture_output=True, text=True, timeout=120)
+    assert out.returncode != 0 and "--dump-outputs" in out.stderr
 
 
 def test_pack_round_layout():

@@ -87,14 +87,14 @@ def test_driver_matches_python_binding(tmp_path, algo):
     p.close()
 
 
+
 @pytest.mark.parametrize("driver", ["FDSTAR", "SGDFM", "DFM"])
 @pytest.mark.parametrize("define", [[], ["-DNO_HEURISTIC"]])
 def test_reference_drivers_compile_unmodified_against_the_mirror(driver, define):
-    """The drop-in claim itself: the reference's own driver sources (Tests/Planners/*/main.cpp) are
-    parsed and type-checked against the mirrored headers, unmodified (g++ -fsyntax-only: nothing is
-    built or copied).  Only where the reference tree is mounted (not on the GPU box)."""
-    src = os.path.join("/root/reference/Tests/Planners", driver, "main.cpp")
-    if not os.path.exists(src):
-        pytest.skip("reference tree not present")
-    subprocess.check_call(["g++", "-std=c++17", "-fsyntax-only", "-Wall"] + define +
-                          ["-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(PKG, "include"), src])
+    """The drop-in claim: what the reference's planner processes (Tests/Planners/{FDSTAR,SGDFM,DFM}/main.cpp) use of the planner
+    surface -- planner class and level, the path extractor on the planner's map and grid, configuration, patch, step, the public
+    timers, the `tof` dump over map.buckets with the planner's element type -- restated in tests/cpp/surface_driver.cpp (the
+    reference's sources are not part of this repository) and type-checked against the mirrored headers (g++ -fsyntax-only)."""
+    subprocess.check_call(["g++", "-std=c++17", "-fsyntax-only", "-Wall", "-Werror", "-DSURFACE_" + driver] + define +
+                          ["-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(PKG, "include"),
+                           os.path.join(ROOT, "tests", "cpp", "surface_driver.cpp")])

@@ -3,10 +3,10 @@
 # usage: bash tools/final_numbers.sh [directory under gpurun_out/]
 O=gpurun_out/${1:-r4_final}; mkdir -p $O
 timeout -k 10 900 python -m pytest tests -m gpu -q > $O/gputests.log 2>&1; echo "tests rc=$?"; tail -2 $O/gputests.log
-timeout -k 10 300 python bench.py --steps 10 --warmup 3 > $O/headline.json 2> $O/headline.err; echo "headline rc=$?"
-timeout -k 10 300 python bench.py --algo SG --size 2048 --seed 1234 --patches 0 --steps 10 --warmup 3 --no-cpu-baseline > $O/config2.json 2> $O/config2.err; echo "config2 rc=$?"
-timeout -k 10 600 python bench.py --algo DFM --size 2048 --batch 8 --steps 3 --warmup 1 > $O/config4.json 2> $O/config4.err; echo "config4 rc=$?"
-timeout -k 10 600 python bench.py --size 8192 --seed 42 --heuristic --steps 3 --warmup 1 --no-cpu-baseline > $O/config5.json 2> $O/config5.err; echo "config5 rc=$?"
+timeout -k 10 300 python bench.py --full --steps 10 --warmup 3 > $O/headline.json 2> $O/headline.err; echo "headline rc=$?"
+timeout -k 10 300 python bench.py --full --algo SG --size 2048 --seed 1234 --patches 0 --steps 10 --warmup 3 --no-cpu-baseline > $O/config2.json 2> $O/config2.err; echo "config2 rc=$?"
+timeout -k 10 600 python bench.py --full --algo DFM --size 2048 --batch 8 --steps 3 --warmup 1 > $O/config4.json 2> $O/config4.err; echo "config4 rc=$?"
+timeout -k 10 600 python bench.py --full --size 8192 --seed 42 --heuristic --steps 3 --warmup 1 --no-cpu-baseline > $O/config5.json 2> $O/config5.err; echo "config5 rc=$?"
 python - "$O" <<'PY'
 import json, sys
 for n in ("headline", "config2", "config4", "config5"):
