@@ -138,7 +138,12 @@ int ufm_check_layout(ufm_t *p, uint64_t *bad_ring_entries, uint64_t *bad_cost_by
  * default: by the size of the job (0.2 s + 4 us per tile); "owned_waves": 16 waves per tile visit and 256 workgroups, 8 and 512, or 0 = by the size of the job;
  * "owned_flags": variants of its scheduler for measurements -- 32: idle workgroups do not visit other owners' tiles, 2: no hand-off of border values during a
  * visit, 16: no activations taken in during a visit -- which change who visits which tile when, never a result);
- * 0: launch chain only.  ufm_stats::resident_* report it. ---- */
+ * 0: launch chain only.  ufm_stats::resident_* report it.
+ * "dfm_follow_info" (default 0; MS-DFM level 1): a replan's invalidation follows the stored back-pointer bytes, as the reference's
+ * DFMPlanner<1> follows INFO (DynamicFastMarching_impl.h:88-99, :124-131) and as the node planners here always do -- an element goes when
+ * a cell its candidate depends on has gone, and only where cell costs changed is its own candidate evaluated -- instead of evaluating
+ * all eight candidates in every sweep.  Results agree within the MS-DFM tolerance, not bit for bit.  UFM_ERR_INVALID for 1 on an
+ * MS-DFM level-0 planner (no Info); accepted without effect by FD / SG. ---- */
 int ufm_set_param(ufm_t *p, const char *name, double value);
 
 /* ---- back-pointers: the `Info` member of a level-1/2 map element (ExpandedMap.h:27-29; set in
@@ -154,14 +159,22 @@ int ufm_set_param(ufm_t *p, const char *name, double value);
  * SG :266-303, DFM :212-268) -- the checker of the stored ones; the two may differ where candidates tie. ---- */
 int ufm_read_info(ufm_t *p, int x0, int y0, int nx, int ny, int32_t *info);
 int ufm_read_info_derived(ufm_t *p, int x0, int y0, int nx, int ny, int32_t *info);
-/* Self-check of the stored back-pointers (node planners; UFM_ERR_INVALID for MS-DFM, whose invalidation does not use them), over the
+/* Self-check of the stored back-pointers (level-1/2 planners; UFM_ERR_INVALID for MS-DFM level 0, which has none), over the
  * whole field: out[0] = elements that hold a value (the goal aside), out[1] = of those without a back-pointer, out[2] = elements BELOW
  * their map's start key whose parent triangle, evaluated on the field as it stands, gives a larger value than the element holds
  * (unsupported), out[3] = whose recorded dependence (on the triangle's edge / diagonal vertex) is not the one that evaluation has,
  * out[4] = whose parent gives a smaller value (elements waiting to be lowered: beyond the start's key in a focused search, none
  * otherwise), out[5] = unsupported elements at / beyond the start's key (invalidations a focused search keeps queued, like the
  * reference's queue entries beyond its end condition).  out[1..3] must be 0 whenever no step is running: the invalidation of a
- * replan follows these bytes without evaluating anything. */
+ * replan follows these bytes without evaluating anything.
+ * MS-DFM level 1: the byte names an axis neighbour and a cell of the perpendicular pair; their candidate (compute_optimal_cost,
+ * DynamicFastMarching_impl.h:322-342) is evaluated with the sweeps' arithmetic and compared with the element's value within 8 ulp --
+ * the slack the MS-DFM invalidation allows, because the lowering leaves values up to a few ulp from their operator (its livelock
+ * guards in tiles that keep coming back).  out[2] / out[5]: larger by more than that, out[4]: smaller by more than that; out[3]:
+ * below the start's key, the dependence bits leave out a cell whose loss would move the candidate by more than that (at the case
+ * boundary, th ~ d, both cases give the value to a few ulp and the recorded case may be the other one).  At / beyond the start's
+ * key such an element is counted in out[5]: its byte belongs to a tile a focused step has left parked, which the lowering visit
+ * that brings it below the key re-evaluates and renews. */
 int ufm_check_info(ufm_t *p, uint64_t out[6]);
 
 /* ---- the queue, read-only: replaces the public member ReplannerBase::priority_queue (ReplannerBase.h:110-115,154;

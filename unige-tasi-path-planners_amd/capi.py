@@ -168,11 +168,13 @@ class Planner:
     num_nodes_updated, num_nodes_expanded, and a dense field view in place of
     ExpandedMap::get_g / get_rhs."""
 
-    def __init__(self, algo, opt_lvl=0, use_heuristic=False, device=0):
+    def __init__(self, algo, opt_lvl=0, use_heuristic=False, device=0, follow_info=False):
         self.L = load_library()
         h = C.c_void_p()
         _chk(self.L.ufm_create(C.byref(h), algo, opt_lvl, int(use_heuristic), device), "ufm_create")
         self.h = h
+        if follow_info:     # MS-DFM level 1: invalidation along the stored back-pointers (ufm_set_param "dfm_follow_info")
+            self.set_param("dfm_follow_info", 1)
         self.algo = algo
         self.stats = Stats()
         self.u_time = 0.0
@@ -301,9 +303,10 @@ class Planner:
 
 
     def check_info(self):
-        """stored back-pointers (node planners): (elements with a value, without a back-pointer, whose parent triangle does not
+        """stored back-pointers (level-1/2 planners): (elements with a value, without a back-pointer, whose parent triangle does not
         give the value but a larger one, whose dependence bits are off, whose parent gives a smaller value -- waiting to be
-        lowered, beyond the start's key --, unsupported ones at / beyond the start's key: queued invalidations); [1:4] are 0 when sound"""
+        lowered, beyond the start's key --, unsupported ones at / beyond the start's key: queued invalidations); [1:4] are 0 when sound.
+        MS-DFM level 1: the named candidate against the value within 8 ulp (include/ufm.h); level 0 raises UfmError (no Info)"""
         out = (C.c_uint64 * 6)()
         _chk(self.L.ufm_check_info(self.h, C.addressof(out)), "ufm_check_info")
         return tuple(int(v) for v in out)
@@ -326,7 +329,7 @@ class BatchPlanner:
     """Batch of independent, equally sized map instances: on one device, or (devices=[...]) spread over several
     in contiguous blocks, one engine per device inside the one handle."""
 
-    def __init__(self, n_maps, algo, opt_lvl=0, use_heuristic=False, device=0, devices=None):
+    def __init__(self, n_maps, algo, opt_lvl=0, use_heuristic=False, device=0, devices=None, follow_info=False):
         self.L = load_library()
         h = C.c_void_p()
         if devices is None:
@@ -336,6 +339,8 @@ class BatchPlanner:
             _chk(self.L.ufm_batch_create_sharded(C.byref(h), n_maps, algo, opt_lvl, int(use_heuristic), arr, len(devices)),
                  "ufm_batch_create_sharded")
         self.h = h
+        if follow_info:     # as Planner's
+            self.set_param("dfm_follow_info", 1)
         self.n = n_maps
         self.algo = algo
         self.stats = Stats()
@@ -429,6 +434,7 @@ class BatchPlanner:
         _chk(self.L.ufm_batch_set_param(self.h, name.encode(), float(value)), "ufm_batch_set_param")
 
     def check_info(self):
+        """as Planner.check_info, summed over the maps"""
         out = (C.c_uint64 * 6)()
         _chk(self.L.ufm_batch_check_info(self.h, C.addressof(out)), "ufm_batch_check_info")
         return tuple(int(v) for v in out)

@@ -358,12 +358,16 @@ __global__ void k_check_layout(DevParams P, unsigned long long *out) {
 }
 // Self-check of the stored back-pointers (ufm_check_info), node planners: every element that holds a value (but the goal) must name a parent
 // triangle, that triangle must give the element's value when it is evaluated on the field as it stands -- bit for bit, with the operator the
-// sweeps use -- and the dep bits must say which vertices that evaluation leans on.  The invalidation follows these bytes blindly (ufm_region.h),
-// so this is the invariant it rests on.  out[0]: elements with a value, out[1]: without a parent, out[2]: whose parent gives a LARGER value
+// sweeps use -- and the dep bits must say which vertices that evaluation leans on.  The invalidation follows these bytes blindly (ufm_region.h;
+// MS-DFM level 1 with "dfm_follow_info", within its 8-ulp slack, see below), so this is the invariant it rests on.  out[0]: elements with a value, out[1]: without a parent, out[2]: whose parent gives a LARGER value
 // (an unsupported element) although the element lies below its map's start key: never; out[3]: whose dep bits differ from the case the evaluation
 // takes; out[4]: whose parent gives a smaller value (an element waiting to be lowered: beyond the start's key in a focused search, nowhere
 // otherwise); out[5]: unsupported elements at or beyond the start's key (invalidations a focused search keeps queued, like the reference's
 // under-consistent queue entries beyond its end condition).
+// MS-DFM level 1: the candidate the byte names -- q_dfm on its axis neighbour and its perpendicular cell --, compared with the element's value
+// within the 8 ulp the invalidation allows (k_relax, ufm_region.h): the lowering's lax / quiet guards leave values that far from their operator.
+// out[3] likewise: a cell the candidate leans on beyond that slack (its loss would move the value by more) that the dep bits leave out, below the
+// start's key; at / beyond it such elements count in out[5].
 template <int ALGO>
 __global__ void k_check_bp(DevParams P, unsigned long long *out) {
     unsigned long long n_val = 0, n_none = 0, n_bad = 0, n_dep = 0, n_low = 0, n_parked = 0;
@@ -383,6 +387,33 @@ __global__ void k_check_bp(DevParams P, unsigned long long *out) {
             const int c = P.cost[(size_t)m * P.cstride + (size_t)cx * P.W + cy];
             return c >= thr ? INFINITY : (float)c;
         };
+        if constexpr (ALGO == ALGO_DFM1) {
+            // axis q: vertical, horizontal, TR-BL, TL-BR (QuadConsts<ALGO_DFM1>: +so / +po as offsets (dx, dy))
+            const int sx = (q == 1) ? 0 : 1, sy = (q == 0) ? 0 : ((q == 2) ? -1 : 1), px = (q == 0) ? 0 : 1, py = (q == 1) ? 0 : ((q == 3) ? -1 : 1);
+            const int sa = h ? 1 : -1, sp = (b & 32) ? 1 : -1;
+            const float tau = cst(x, y), th = (q & 2) ? tau * SQRT2F : tau;
+            const float ga = val(x + sa * sx, y + sa * sy), gp = val(x + sp * px, y + sp * py);
+            const float r = q_dfm(ga, gp, th);
+            const int ug = __float_as_int(g), ur = __float_as_int(r);
+            auto below_key = [&]() { const float B = P.dyn->focused ? start_bound(P, m) : INFINITY; return g + tile_heuristic(P, m, x / T, y / T) < B || B == INFINITY; };
+            if (r == INFINITY || r != r || ur - ug > 8) {
+                if (below_key()) ++n_bad; else ++n_parked;
+            }
+            else if (ug - ur > 8) ++n_low;
+            else {
+                // dep: where the case sits on its boundary (th ~ d) the two cases give the same value to a few ulp, and the case can flip with an ulp
+                // of a neighbour after the byte was written -- what the invalidation needs is that no cell the value leans on BEYOND the slack is
+                // left out of the recorded bits: with such a cell at +inf the candidate must stay within 8 ulp (extra bits only cost a re-lowering).
+                // At / beyond the start's key such a byte is one a focused step has not renewed yet -- the element's tile is parked, and the lowering
+                // visit that brings it below the key re-evaluates it (replace semantics) and renews its byte --: counted with the queued work there
+                const int miss = dep_dfm(ga, gp, th) & ~(b & 3);
+                auto moved = [&](float v) { return v == INFINITY || abs(__float_as_int(v) - ur) > 8; };
+                if (((miss & 1) && moved(q_dfm(INFINITY, gp, th))) || ((miss & 2) && moved(q_dfm(ga, INFINITY, th)))) {
+                    if (below_key()) ++n_dep; else ++n_parked;
+                }
+            }
+            continue;
+        }
         const int cx = x - 1 + (q >> 1), cy = y - 1 + (q & 1);                  // the triangle's cell
         const float c = cst(cx, cy), g1 = h ? val(x, y + dy) : val(x + dx, y), g2 = val(x + dx, y + dy);
         float r; int dep;
@@ -487,7 +518,7 @@ __device__ void tile_bp(const DevParams &P, int gt, int thr, float *Gs, float *C
         C.load(Cs, lx, ly, q);
         const LaneEval le = eval_quad_w<ALGO>(Gs + (lx + 1) * GP + ly + 1, q, C);
         const float nv = quad_min(le.r);
-        const int bq = quad_min_int(bp_byte<ALGO>(le, q, C, le.r == nv)), b = bq == 0x3FF ? BP_NONE : (bq & 0x1F);
+        const int bq = quad_min_int(bp_byte<ALGO>(le, q, C, le.r == nv)), b = bp_of_key<ALGO>(bq);
         if (q == 0) P.bp[(size_t)gt * TT + lx * T + ly] = (uint8_t)((x0 + lx == goal_x && y0 + ly == goal_y) ? BP_NONE : b);
     }
     __syncthreads();

@@ -161,6 +161,12 @@ enum { MODE_LOWER = 0, MODE_RAISE = 1 };
 // 256^2..1024^2: <= 2.45e-6 / 27 ulp with 60-90 % of the elements off, against <= 1.03e-6 / 10 ulp with 0.3-33 %.
 constexpr int ALGO_DFM1 = 3;
 template <int ALGO> constexpr bool is_dfm = (ALGO == ALGO_DFM1);
+// Flag or-ed into the operator id of the invalidation kernels (k_relax<., MODE_RAISE>, k_replan_region): MS-DFM level 1 invalidates along the
+// stored back-pointer bytes, as the node planners always do (ufm_set_param "dfm_follow_info").  A distinct instantiation, so that the
+// default one is untouched; the kernels strip it (algo_of) before anything else sees the id.
+constexpr int ALGO_FOLLOW_INFO = 0x10;
+constexpr int ALGO_DFM1_INFO = ALGO_DFM1 | ALGO_FOLLOW_INFO;
+constexpr int algo_of(int algof) { return algof & ~ALGO_FOLLOW_INFO; }
 
 constexpr int LMAX = 8192;
 constexpr int INFBITS = 0x7F800000;   // +inf as int: non-negative floats order like their bits

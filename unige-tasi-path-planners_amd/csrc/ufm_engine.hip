@@ -197,13 +197,14 @@ static int engine_check_layout(Engine *e, uint64_t *bad_ring, uint64_t *bad_cost
 int ufm_check_layout(ufm_t *p, uint64_t *bad_ring, uint64_t *bad_cost) { return p ? engine_check_layout(p->e, bad_ring, bad_cost) : UFM_ERR_INVALID; }
 static int engine_check_info(Engine *e, uint64_t out[6]) {
     if (!e || !e->allocated || !out) return UFM_ERR_INVALID;
-    if (e->algo == UFM_ALGO_DFM) return UFM_ERR_INVALID;       // (MS-DFM invalidates by evaluation: its bytes are for ufm_read_info only)
+    if (e->algo == UFM_ALGO_DFM && e->opt_lvl == 0) return UFM_ERR_INVALID;       // (MS-DFM level 0: its map has no Info, there are no bytes)
     for (const MapState &ms : e->maps) if (!ms.have_map) return UFM_ERR_INVALID;
     HIPCHK(hipSetDevice(e->device));
     { int rc = e->flush_deferred(); if (rc != UFM_OK) return rc; }
     unsigned long long *d_acc = reinterpret_cast<unsigned long long *>(e->d_scratch);
     HIPCHK(hipMemsetAsync(d_acc, 0, 6 * sizeof(unsigned long long), e->stream));
     if (e->algo == UFM_ALGO_SG) k_check_bp<UFM_ALGO_SG><<<1024, 256, 0, e->stream>>>(e->P, d_acc);
+    else if (e->algo == UFM_ALGO_DFM) k_check_bp<ALGO_DFM1><<<1024, 256, 0, e->stream>>>(e->P, d_acc);
     else k_check_bp<UFM_ALGO_FD><<<1024, 256, 0, e->stream>>>(e->P, d_acc);
     unsigned long long h[6] = {0, 0, 0, 0, 0, 0};
     HIPCHK(hipMemcpyAsync(h, d_acc, sizeof(h), hipMemcpyDeviceToHost, e->stream));
@@ -285,6 +286,10 @@ static int engine_set_param(Engine *e, const char *name, double value) {
     else if (!std::strcmp(name, "dag_kappa")) e->dag_kappa = (float)value;
     else if (!std::strcmp(name, "dag_patience")) e->dag_patience = value < 1 ? 1 : (int)value;
     else if (!std::strcmp(name, "dynamic")) e->dynamic_mode = value != 0.0;
+    else if (!std::strcmp(name, "dfm_follow_info")) {         // MS-DFM level 1: invalidation along the stored bytes (no effect on FD / SG, which always do)
+        if (value != 0.0 && e->algo == UFM_ALGO_DFM && e->opt_lvl == 0) return UFM_ERR_INVALID;
+        e->dfm_follow_info = value != 0.0 && e->algo == UFM_ALGO_DFM;
+    }
     else return UFM_ERR_INVALID;
     return UFM_OK;
 }

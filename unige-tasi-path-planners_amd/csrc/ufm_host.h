@@ -60,6 +60,7 @@ struct Engine {
     bool dag_have = false;           // ... an estimate is in P.dag_a
     float dag_kappa = 0.5f;          // ... a neighbour counts as clearly earlier below own estimate - kappa x (own - earliest neighbour's)
     int dag_patience = 16;           // ... looks without an eligible tile before a workgroup takes a held one anyway
+    bool dfm_follow_info = false;    // MS-DFM level 1: the invalidation follows the stored back-pointer bytes (k_relax / k_replan_region<ALGO_DFM1_INFO>)
     bool use_region = true;          // replans: one workgroup runs both phases in LDS on the block around the patch (ufm_region.h);
                                      // the launch chain only takes over when work is left outside the block
     int region_ahead = 2;            // block placement: tiles kept between the patches' centre and the block's goal-side edge
@@ -75,7 +76,7 @@ struct Engine {
     int batch_margin = 1;            // replans: launches per phase = most that the last 6 replans needed + this
     float raise_margin = 0.25f;      // invalidation bound = start key + this many ordering bands (a miss costs a second round)
     ReplanJob *h_job = nullptr;      // host-coherent pinned: per-replan inputs of the graph's first node
-    struct GraphSig { DevParams P; float band, delta; int max_iters, grid; };
+    struct GraphSig { DevParams P; float band, delta; int max_iters, grid, follow; };
     GraphSig graph_sig{};
     std::vector<std::pair<int, hipGraphExec_t>> graphs;   // key nr * 256 + nl
     int relax_kernel(int mode, int k_arg, float rbound, int grid);
@@ -384,6 +385,7 @@ int Engine::relax_kernel(int mode, int k_arg, float rbound, int grid) {
     } else {
         if (algo == UFM_ALGO_FD) UFM_LAUNCH(UFM_ALGO_FD, MODE_RAISE);
         else if (algo == UFM_ALGO_SG) UFM_LAUNCH(UFM_ALGO_SG, MODE_RAISE);
+        else if (dfm_follow_info) UFM_LAUNCH(ALGO_DFM1_INFO, MODE_RAISE);
         else UFM_LAUNCH(ALGO_DFM1, MODE_RAISE);
     }
 #undef UFM_LAUNCH
@@ -397,7 +399,7 @@ int Engine::relax_kernel(int mode, int k_arg, float rbound, int grid) {
 int Engine::replan_graph(int nr, int nl, float band, hipGraphExec_t *out) {
     GraphSig sig{};
     sig.P = P; sig.band = band; sig.delta = delta_abs >= 0.0f ? delta_abs : delta_scale * T * mean_cost;
-    sig.max_iters = max_iters; sig.grid = grid_relax * 4096 + tail_grid;
+    sig.max_iters = max_iters; sig.grid = grid_relax * 4096 + tail_grid; sig.follow = dfm_follow_info ? 1 : 0;
     if (std::memcmp(&sig, &graph_sig, sizeof(GraphSig)) != 0) { drop_graphs(); std::memcpy(&graph_sig, &sig, sizeof(GraphSig)); }
     const int key = nr * 256 + nl;
     for (auto &g : graphs) if (g.first == key) { *out = g.second; return UFM_OK; }
@@ -458,6 +460,7 @@ int Engine::launch_relax(int mode, float rbound, hipEvent_t e0, hipEvent_t e1) {
     } else {
         if (algo == UFM_ALGO_FD) UFM_LAUNCH(UFM_ALGO_FD, MODE_RAISE);
         else if (algo == UFM_ALGO_SG) UFM_LAUNCH(UFM_ALGO_SG, MODE_RAISE);
+        else if (dfm_follow_info) UFM_LAUNCH(ALGO_DFM1_INFO, MODE_RAISE);
         else UFM_LAUNCH(ALGO_DFM1, MODE_RAISE);
     }
 #undef UFM_LAUNCH
@@ -946,7 +949,8 @@ int Engine::step(ufm_stats *out) {
                            else k_replan_region<A><<<g, b, 0, stream>>>(P, rjs, h_ctr, h_flag); } while (0)
             if (algo == UFM_ALGO_FD) UFM_LAUNCH(UFM_ALGO_FD);
             else if (algo == UFM_ALGO_SG) UFM_LAUNCH(UFM_ALGO_SG);
-                    else UFM_LAUNCH(ALGO_DFM1);
+            else if (dfm_follow_info) UFM_LAUNCH(ALGO_DFM1_INFO);
+            else UFM_LAUNCH(ALGO_DFM1);
 #undef UFM_LAUNCH
             HIPCHK(hipGetLastError());
             last_active = 1;

@@ -94,6 +94,12 @@ __device__ __forceinline__ float q_dfm(float a, float b, float th) {
     const float s = ((ga + gb) + sqrt_rn(2.0f * (th * th) - d * d)) * 0.5f;
     return (th > d) ? s : (ga + th);        // both inf -> d NaN -> ga + th = inf
 }
+// ... and which of its two inputs that value leans on (bit 0: a, bit 1: b): the quadratic case both; "min(a, b) + th" the smaller alone (a tie: both).
+// With the other input at +inf the same case is taken and gives the same value -- the rule the node planners' dep bits rest on.
+__device__ __forceinline__ int dep_dfm(float a, float b, float th) {
+    const float d = fmaxf(a, b) - fminf(a, b);
+    return (th > d) ? 3 : ((a < b) ? 1 : ((b < a) ? 2 : 3));
+}
 
 // ---- quad evaluation ---------------------------------------------------------------------
 // The eight triangles around a node split naturally by the cell they lie in.  Four adjacent
@@ -165,6 +171,8 @@ __device__ __forceinline__ float quad_min(float v) {
 // code, node planners: (q << 1) | h -- the triangle of cell q (the quad lane that evaluated it) whose edge neighbour p1 is the vertical (h = 0) or the
 // horizontal one (h = 1); its other vertex p2 is the diagonal node of that cell.  MS-DFM level 0: the stencil (0 orthogonal, 1 diagonal); level 1:
 // (q << 1) | which of the axis's two neighbours (0: -so, 1: +so).  Of several candidates that tie, the lowest code.
+// MS-DFM level 1 adds bit 5: which cell of the perpendicular pair the candidate took (0: -po, 1: +po; a tie as best_cell breaks it) -- the byte is
+// (pp << 5) | (code << 2) | dep, at most 0x3F, so BP_NONE stays distinct.
 // dep, node planners: which of the two vertices the value depends on -- bit 0: G(p1), bit 1: G(p2) -- by the case compute_optimal_cost took
 // Tied candidates (round 4): the one the reference's min_rhs<1>() would keep -- it walks Graph::neighbors_8 (top, top-left, left, bottom-left, bottom,
 // bottom-right, right, top-right: Graph.cpp:71-85) and lets the LAST tied neighbour win (`if (rhs == cost) bptr = ...`, FD impl:196-208) --, so that the
@@ -172,7 +180,8 @@ __device__ __forceinline__ float quad_min(float v) {
 // views parted on the 7-8 % of the nodes whose triangles over one grid edge tie).  bp_ref(code) = that neighbour's position in neighbors_8.
 // (FD impl:292-319, SG :422-436): "g1 + ..." (III, B) leans on p1 alone, "g2 + ..." (I, A) on p2 alone, the interpolated case (II) on both.  With the other
 // vertex at +inf the same case is taken and gives the same value, so: an element is gone exactly when a vertex it depends on is gone (the invalidation of
-// ufm_region.h follows these bits without evaluating anything).  MS-DFM: 3.
+// ufm_region.h follows these bits without evaluating anything).  MS-DFM level 1: bit 0 G(axis neighbour), bit 1 G(perpendicular cell), by the case
+// q_dfm took (dep_dfm) -- the same rule.
 constexpr int BP_NONE = 0xFF;
 // code (q << 1) | h -> index in Graph::neighbors_8 of the node b with RHS(s) = cost(s, b, ccw_neighbor(s, b)): codes 0..7 -> 1 2 0 7 4 3 5 6
 __device__ __forceinline__ int bp_ref(int code) { return (0x65347021u >> (4 * code)) & 7; }
@@ -186,16 +195,22 @@ __device__ __forceinline__ int dep_fd(float g1, float g2, const CellFD &K, const
 }
 // A lane's evaluation with what the back-pointer needs: r = the smaller of the lane's candidates, h = it was the second one, and (node planners) the
 // three neighbour values it was computed from.
-struct LaneEval { float r; bool h; float gV, gH, gD; };
+// (MS-DFM: xb = the byte's bits beside the code -- (pp << 5) | dep, see bp_byte.)
+struct LaneEval { float r; bool h; float gV, gH, gD; int xb; };
 template <int ALGO, int GPITCH = GP>
 __device__ __forceinline__ LaneEval eval_quad_w(const float *ctr, int q, const QuadConsts<ALGO> &C) {
     LaneEval e;
     e.gV = e.gH = e.gD = 0.0f;
+    e.xb = 0;
     if constexpr (ALGO == ALGO_DFM1) {
-        const float pm = fminf(ctr[-C.po], ctr[C.po]);
-        const float a = q_dfm(ctr[-C.so], pm, C.th), b = q_dfm(ctr[C.so], pm, C.th);
+        const float pn = ctr[-C.po], pq = ctr[C.po], pm = fminf(pn, pq);
+        const float gn = ctr[-C.so], gq = ctr[C.so];
+        const float a = q_dfm(gn, pm, C.th), b = q_dfm(gq, pm, C.th);
         e.h = b < a;
         e.r = e.h ? b : a;
+        // which cell of the pair: the one the reference's best_cell picks (impl:284-296, a tie to its second argument: +po, for axis 3 -po)
+        const bool pp = (q == 3) ? (pq < pn) : !(pn < pq);
+        e.xb = (pp ? 32 : 0) | dep_dfm(e.h ? gq : gn, pm, C.th);
     } else {
         const int sx = (q & 2) ? GPITCH : -GPITCH, sy = (q & 1) ? 1 : -1;
         e.gD = ctr[sx + sy]; e.gV = ctr[sx]; e.gH = ctr[sy];
@@ -218,8 +233,22 @@ __device__ __forceinline__ int bp_byte(const LaneEval &e, int q, const QuadConst
         t.bp = e.h ? C.th.bp : C.tv.bp; t.cbp = e.h ? C.th.cbp : C.tv.cbp; t.bI = e.h ? C.th.bI : C.tv.bI;
         dep = dep_fd(e.h ? e.gH : e.gV, e.gD, C.k, t);
     }
-    if constexpr (ALGO == ALGO_DFM1) return winner ? ((code << 2) | dep) : 0x3FF;          // (MS-DFM: the lowest code)
+    if constexpr (ALGO == ALGO_DFM1) {      // (MS-DFM: the lowest code -- the key puts it above the byte; bp_of_key keeps the byte's 6 bits)
+        return winner ? ((code << 6) | (code << 2) | e.xb) : 0x3FF;
+    }
     return winner ? (((7 - bp_ref(code)) << 5) | (code << 2) | dep) : 0x3FF;      // (quad_min_int: the tied candidate latest in neighbors_8 order; the byte = its low 5 bits)
+}
+// the byte from the quad's smallest key (0x3FF: no lane won -> BP_NONE)
+template <int ALGO>
+__device__ __forceinline__ int bp_of_key(int bq) { return bq == 0x3FF ? BP_NONE : (bq & (ALGO == ALGO_DFM1 ? 0x3F : 0x1F)); }
+// MS-DFM level 1, the LDS offsets of the two cells a byte names, for a field of pitch GPITCH (the offsets of QuadConsts<ALGO_DFM1>)
+template <int GPITCH>
+__device__ __forceinline__ void dfm_bp_offsets(int bpb, int &oa, int &op) {
+    const int bq = (bpb >> 3) & 3;
+    const int so = (bq == 0) ? GPITCH : (bq == 1) ? 1 : (bq == 2) ? GPITCH - 1 : GPITCH + 1;
+    const int po = (bq == 0) ? 1 : (bq == 1) ? GPITCH : (bq == 2) ? GPITCH + 1 : GPITCH - 1;
+    oa = (bpb & 4) ? so : -so;
+    op = (bpb & 32) ? po : -po;
 }
 __device__ __forceinline__ int quad_min_int(int v) {
     v = min(v, __builtin_amdgcn_update_dpp(v, v, 0xB1, 0xF, 0xF, false));   // quad_perm [1,0,3,2]
@@ -228,21 +257,28 @@ __device__ __forceinline__ int quad_min_int(int v) {
 // Node planners, invalidation: the value the element's OWN parent triangle (stored byte bpb) gives now -- what the reference's level-1/2 planners
 // look at when a neighbour is raised (FD impl:100-110: only elements whose back-pointer involves the raised node are recomputed).  +inf from the
 // lanes of the other cells (and from every lane when there is no parent: the quad's min is then +inf, and a finite value without a parent goes).
+// MS-DFM level 1 (dfm_follow_info): the candidate the byte names -- its axis neighbour and its perpendicular cell, not the better of the pair --
+// in the lane of its axis; no parent (BP_NONE) gives +inf.
 template <int ALGO, int GPITCH = GP>
 __device__ __forceinline__ float eval_quad_bp(const float *ctr, int q, const QuadConsts<ALGO> &C, int bpb) {
-    static_assert(ALGO == UFM_ALGO_FD || ALGO == UFM_ALGO_SG, "node planners");
-    const int bpc = bpb >> 2;
-    const int sx = (q & 2) ? GPITCH : -GPITCH, sy = (q & 1) ? 1 : -1;
-    const bool h = bpc & 1;
-    const float gD = ctr[sx + sy], g1 = ctr[h ? sy : sx];
-    float r;
-    if constexpr (ALGO == UFM_ALGO_SG) r = tri_sg(g1, gD, C.k);
-    else {
-        TriFD t;
-        t.bp = h ? C.th.bp : C.tv.bp; t.cbp = h ? C.th.cbp : C.tv.cbp; t.bI = h ? C.th.bI : C.tv.bI;
-        r = tri_fd(g1, gD, C.k, t);
+    if constexpr (ALGO == ALGO_DFM1) {
+        const float a = ctr[(bpb & 4) ? C.so : -C.so], p = ctr[(bpb & 32) ? C.po : -C.po];
+        return (((bpb >> 3) & 3) == q && bpb != BP_NONE) ? q_dfm(a, p, C.th) : INFINITY;
+    } else {
+        static_assert(ALGO == UFM_ALGO_FD || ALGO == UFM_ALGO_SG, "node planners");
+        const int bpc = bpb >> 2;
+        const int sx = (q & 2) ? GPITCH : -GPITCH, sy = (q & 1) ? 1 : -1;
+        const bool h = bpc & 1;
+        const float gD = ctr[sx + sy], g1 = ctr[h ? sy : sx];
+        float r;
+        if constexpr (ALGO == UFM_ALGO_SG) r = tri_sg(g1, gD, C.k);
+        else {
+            TriFD t;
+            t.bp = h ? C.th.bp : C.tv.bp; t.cbp = h ? C.th.cbp : C.tv.cbp; t.bI = h ? C.th.bI : C.tv.bI;
+            r = tri_fd(g1, gD, C.k, t);
+        }
+        return (bpc >> 1) == q ? r : INFINITY;
     }
-    return (bpc >> 1) == q ? r : INFINITY;
 }
 // ctr points at the node inside the LDS tile; returns this lane's share of RHS(node)
 template <int ALGO, int GPITCH = GP>

@@ -419,11 +419,12 @@ __device__ float dfm_stencil(int ca, int cb, float ga, float gb, float tau, floa
     return ga + tau * h;
 }
 
-// The stored bytes ((code << 2) | dep, ufm_engine.hip; BP_NONE: the goal, or an element that never got a value -> -1, -1; likewise an
+// The stored bytes ((code << 2) | dep, MS-DFM level 1 with the perpendicular cell in bit 5: ufm_ops.h bp_byte; BP_NONE: the goal, or an element that never got a value -> -1, -1; likewise an
 // element whose value is +inf).  Node planners, code (q << 1) | h: the triangle of cell q -- (x-1+dx, y-1+dy), dx = q >> 1, dy = q & 1 -- over the vertical (h = 0) or the
 // horizontal (h = 1) neighbour p1 and the diagonal node p2 of that cell; b is the one of the two whose ccw_neighbor is the other.
 // MS-DFM level 1, code (q << 1) | w: the candidate of min_rhs_decreased_neighbor (impl:270-313) built on the neighbour w of axis q (vertical,
-// horizontal, TR-BL, TL-BR) and the better cell of the perpendicular pair; out = the pair compute_optimal_cost leaves (impl:322-342).
+// horizontal, TR-BL, TL-BR) and the cell of the perpendicular pair that bit 5 names (1: +po of QuadConsts<ALGO_DFM1>; written as best_cell picks it,
+// impl:284-296); out = the pair compute_optimal_cost leaves (impl:322-342).
 __global__ void k_info_stored(PathField F, const uint8_t *bp, int x0, int y0, int nx, int ny, int32_t *out) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= nx * ny) return;
@@ -437,11 +438,11 @@ __global__ void k_info_stored(PathField F, const uint8_t *bp, int x0, int y0, in
         const int q = (code >> 3) & 3, w = (code >> 2) & 1;      // the byte: (((q << 1) | w) << 2) | dep
         if (F.cells) {
             const int NX[4][2] = {{-1, 1}, {0, 0}, {-1, 1}, {-1, 1}}, NY[4][2] = {{0, 0}, {-1, 1}, {1, -1}, {-1, 1}};
-            // the perpendicular pair in the reference's argument order (best_cell: a tie goes to the second)
-            const int PAX[4] = {0, -1, -1, 1}, PAY[4] = {-1, 0, -1, -1}, PBX[4] = {0, 1, 1, -1}, PBY[4] = {1, 0, 1, 1};
+            // the perpendicular cell the byte names: +po = (0, 1), (1, 0), (1, 1), (1, -1) for axis 0..3
+            const int POX[4] = {0, 1, 1, 1}, POY[4] = {1, 0, 1, -1}, ps = (code & 32) ? 1 : -1;
             const int qx = x + NX[q][w], qy = y + NY[q][w];
-            int px, py; float gp;
-            dfm_best(F, x + PAX[q], y + PAY[q], x + PBX[q], y + PBY[q], px, py, gp);
+            const int px = x + ps * POX[q], py = y + ps * POY[q];
+            const float gp = field_at(F, px, py);
             auto lin = [&](int ax, int ay) { return elem_ok(F, ax, ay) ? ax * F.EY + ay : -2; };
             dfm_stencil(lin(qx, qy), lin(px, py), field_at(F, qx, qy), gp, raster_cost(F, x, y), q < 2 ? 1.0f : PATH_SQRT2, b0, b1);
         } else {

@@ -142,10 +142,13 @@ __device__ __forceinline__ float region_lower_bound(const float *Gs, const Regio
 }
 
 // One phase (MODE_RAISE: invalidation, MODE_LOWER: lowering) of the block to quiescence.  All 16 waves call.
-template <int ALGO, int MODE>
+// ALGOF: the operator id, with ALGO_FOLLOW_INFO for MS-DFM level 1's invalidation along its stored bytes.
+template <int ALGOF, int MODE>
 __device__ void region_phase(const DevParams &P, const RegionJob &J, float *Gs, const uint8_t *Cb, uint8_t *Bb, RegionShared &S,
                              int thr, float hm, int focused, int goal_lx, int goal_ly) {
-    constexpr bool BPRAISE = MODE == MODE_RAISE && !is_dfm<ALGO>;   // invalidation along the stored back-pointers (k_relax)
+    constexpr int ALGO = algo_of(ALGOF);
+    constexpr bool FOLLOW = (ALGOF & ALGO_FOLLOW_INFO) != 0;
+    constexpr bool BPRAISE = MODE == MODE_RAISE && (!is_dfm<ALGO> || FOLLOW);   // invalidation along the stored back-pointers (k_relax)
     const int tid = threadIdx.x, w = wave_index16(tid >> 6), lane = tid & 63;
     const int q = lane & 3, nd = lane >> 2;
     const int nprow = J.ntx * TP, npcol = J.nty * TP;
@@ -220,10 +223,13 @@ __device__ void region_phase(const DevParams &P, const RegionJob &J, float *Gs, 
                 float *ctr = Gs + (lx + 1) * RP + ly + 1;
                 uint8_t *bpp = Bb + lx * RBP + ly;
                 const int bpb = BPRAISE ? *bpp : BP_NONE;
-                // the two vertices of the element's parent triangle (LDS offsets) and whether its value depends on them
+                // the two vertices of the element's parent triangle (LDS offsets) and whether its value depends on them (MS-DFM: the axis neighbour
+                // and the perpendicular cell of its candidate; an element without one has no support)
                 const int bqc = bpb >> 3, bsx = (bqc & 2) ? RP : -RP, bsy = (bqc & 1) ? 1 : -1;
-                const int bo1 = (bpb & 4) ? bsy : bsx, bo2 = bsx + bsy;
+                int bo1 = (bpb & 4) ? bsy : bsx, bo2 = bsx + bsy;
+                if constexpr (is_dfm<ALGO>) dfm_bp_offsets<RP>(bpb, bo1, bo2);
                 const bool bd1 = bpb & 1, bd2 = bpb & 2;
+                const bool bnone = is_dfm<ALGO> && bpb == BP_NONE;
                 const bool goal = (lx == goal_lx) & (ly == goal_ly);
                 // wake targets: lane 0..8 = the 3x3 patches around this one (lane 4: itself).  Which wave a neighbouring patch belongs to and how far its
                 // bit lies from this patch's own do not depend on the patch (wt_*, above the loop): per burst only the position and the range test are left
@@ -267,7 +273,7 @@ __device__ void region_phase(const DevParams &P, const RegionJob &J, float *Gs, 
                     float nv;
                     if constexpr (BPRAISE) {
                         if (arith && b == 0) nv = quad_min(eval_quad_bp<ALGO, RP>(ctr, q, C, bpb));
-                        else { const float p1 = ctr[bo1], p2 = ctr[bo2]; nv = ((bd1 && p1 == INFINITY) || (bd2 && p2 == INFINITY)) ? INFINITY : g; }   // (both loads asked for at once)
+                        else { const float p1 = ctr[bo1], p2 = ctr[bo2]; nv = ((bd1 && p1 == INFINITY) || (bd2 && p2 == INFINITY) || bnone) ? INFINITY : g; }   // (both loads asked for at once)
                     }
                     else nv = quad_min(eval_quad<ALGO, RP>(ctr, q, C));
                     if (goal) nv = 0.0f;
@@ -329,7 +335,7 @@ __device__ void region_phase(const DevParams &P, const RegionJob &J, float *Gs, 
             if (lane == 0) atomicAdd(&S.idle, 1);
             UFM_REGION_SETPRIO(0);
             for (;;) {
-                __builtin_amdgcn_s_sleep((MODE == MODE_RAISE && !is_dfm<ALGO>) ? UFM_REGION_IDLE_SLEEP_RAISE : UFM_REGION_IDLE_SLEEP);
+                __builtin_amdgcn_s_sleep(BPRAISE ? UFM_REGION_IDLE_SLEEP_RAISE : UFM_REGION_IDLE_SLEEP);
                 // (all loads first, then the decisions: one LDS round trip per look)
                 const int idle_now = __hip_atomic_load(&S.idle, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 const int gave_up_now = __hip_atomic_load(&S.giveup, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -360,8 +366,9 @@ __device__ void region_phase(const DevParams &P, const RegionJob &J, float *Gs, 
     __syncthreads();
 }
 
-template <int ALGO>
+template <int ALGOF>   // (the operator id, with ALGO_FOLLOW_INFO: region_phase)
 __global__ __launch_bounds__(NTHR) void k_replan_region(DevParams P, RegionJobs JS, DevCounters *host, unsigned int *flag) {
+    constexpr int ALGO = algo_of(ALGOF);
     __shared__ float Gs[(RN + 2) * RP];
     __shared__ uint8_t Cb[(RN + 1) * RCP];
     __shared__ __attribute__((aligned(16))) uint8_t Bb[RN * RBP];
@@ -608,7 +615,7 @@ __global__ __launch_bounds__(NTHR) void k_replan_region(DevParams P, RegionJobs 
     // ---- 2. invalidate, lower; again while an invalidation that was held back lies below the start's new key ----
     for (int round = 0;; ++round) {
         for (;;) {
-            region_phase<ALGO, MODE_RAISE>(P, J, Gs, Cb, Bb, S, thr, hm, focused, goal_lx, goal_ly);
+            region_phase<ALGOF, MODE_RAISE>(P, J, Gs, Cb, Bb, S, thr, hm, focused, goal_lx, goal_ly);
             // a tile that lost a value after some of its patches had been held back: those patches again
             const int again_t = __syncthreads_or(tid < ntl && S.traised[tid] && S.dprio[1][tid] != INFBITS) && !S.giveup;
             __syncthreads();
@@ -697,7 +704,7 @@ __global__ __launch_bounds__(NTHR) void k_replan_region(DevParams P, RegionJobs 
                 C.load_at(cost_at, lx, ly, q, RP);
                 const LaneEval le = eval_quad_w<ALGO, RP>(Gs + (lx + 1) * RP + ly + 1, q, C);
                 const float nv = quad_min(le.r);
-                const int bq = quad_min_int(bp_byte<ALGO>(le, q, C, le.r == nv)), b = bq == 0x3FF ? BP_NONE : (bq & 0x1F);
+                const int bq = quad_min_int(bp_byte<ALGO>(le, q, C, le.r == nv)), b = bp_of_key<ALGO>(bq);
                 if (q == 0) Bb[lx * RBP + ly] = (uint8_t)((lx == goal_lx && ly == goal_ly) ? BP_NONE : b);
                 if (lane == 0) S.tbp[(pr / TP) * J.nty + pc / TP] = 1;
             }

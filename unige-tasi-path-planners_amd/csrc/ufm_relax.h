@@ -16,8 +16,12 @@
 // balance, used while the queue is long); !DYN: triage fused as described above (short queues).
 // OWN: the resident form (one launch per lowering phase): no lists at all, every workgroup serves the tiles it owns
 // from their queue words (own_push above) until all of them, everywhere, are empty.
-template <int ALGO, int MODE, bool DYN, int OWNK = 0>   // OWNK: 0 launch chain, 1 resident with 16 waves per visit, 2 resident with 8
+// ALGOF: the operator id; with ALGO_FOLLOW_INFO (MODE_RAISE, MS-DFM level 1) the invalidation follows the stored bytes as the node planners' does
+template <int ALGOF, int MODE, bool DYN, int OWNK = 0>   // OWNK: 0 launch chain, 1 resident with 16 waves per visit, 2 resident with 8
 __global__ __launch_bounds__(OWNK == 2 ? NTHR / 2 : NTHR, UFM_RELAX_WAVES) void k_relax(DevParams P, int k_arg, float delta, float rbound, int max_sweeps) {
+    constexpr int ALGO = algo_of(ALGOF);
+    // invalidation along the stored back-pointers: the node planners always, MS-DFM level 1 when asked for
+    constexpr bool BPRAISE = MODE == MODE_RAISE && (!is_dfm<ALGO> || (ALGOF & ALGO_FOLLOW_INFO) != 0);
     constexpr bool OWN = OWNK != 0;
     static_assert(!OWN || (!DYN && MODE == MODE_LOWER), "the resident kernel lowers");
     // The resident kernel can give a tile visit 8 waves instead of 16 and run two visits per CU: during the sweeps about five of a
@@ -61,7 +65,7 @@ __global__ __launch_bounds__(OWNK == 2 ? NTHR / 2 : NTHR, UFM_RELAX_WAVES) void 
 #ifdef UFM_TIMING
     __shared__ unsigned int s_misc_vi;
 #endif
-    __shared__ uint8_t Bs[(MODE == MODE_RAISE && !is_dfm<ALGO>) ? TT : 1];   // the tile's back-pointer bytes (invalidation of the node planners)
+    __shared__ uint8_t Bs[BPRAISE ? TT : 1];   // the tile's back-pointer bytes (invalidation of the node planners, and of MS-DFM level 1 when it follows them)
     __shared__ int s_qw[2];       // in-visit refresh: [0] this tile's queue word as an idle wave last saw it (loaded straight into LDS), [1] refreshes of this visit
 
     const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
@@ -383,7 +387,6 @@ __global__ __launch_bounds__(OWNK == 2 ? NTHR / 2 : NTHR, UFM_RELAX_WAVES) void 
         // (thread ht == -1 loads the record's "complete" flag)
         const float sv = (DIRWAKE && ht >= -1) ? ld_f<OWN>(&seen[ht >= 0 ? ht : RING - 1]) : 0.0f;
         const int c0 = ct[tid < CN ? tid : 0];
-        constexpr bool BPRAISE = MODE == MODE_RAISE && !is_dfm<ALGO>;   // invalidation along the stored back-pointers
         const int bp0 = BPRAISE ? P.bp[(size_t)gt * TT + (io_on ? tid : 0)] : BP_NONE;
         const int goal_x = P.goal[2 * m], goal_y = P.goal[2 * m + 1];   // (with the rest: read after the barrier they cost two more round trips)
         // resident kernel: the values of the map's start elements, one per lane (for the end condition below)
