@@ -12,10 +12,13 @@
 // LinearInterpolationPathExtractor, reset / set_* / patch_map / step / extract_path, u_time,
 // p_time, e_time, map.size(), map.buckets.
 //
-//   ufm_planner [--planner FD|SG|DFM] [--level K] [--max-moves N] <fifo_in> <fifo_out>
+//   ufm_planner [--planner FD|SG|DFM] [--level K] [--max-moves N] [--verify-follow] <fifo_in> <fifo_out>
 //        start, goal and the `tof` flag arrive in-band after the map (DFM/main.cpp:62-67)
 //   ufm_planner [...] <mapfile> <from_x> <from_y> <to_x> <to_y> <cspace> <fifo_in> <fifo_out> <gui> <tof> <outpath>
 //        the 11-argument form of FDSTAR/main.cpp:16-31 and SGDFM/main.cpp
+// With `tof` the expanded-element dump after every step is kept up to date from the steps' deltas (ExpandedMap::follow_changes), not
+// read back whole; --verify-follow also builds it the old way every step -- a read of the whole field through a second view of the
+// same planner -- and ends the run (exit code 3) if the two differ in any element, value, Info or order.
 // Keys with the heuristic term unless compiled with -DNO_HEURISTIC (binary ufm_planner_no_heur),
 // as for the reference's *_no_heur targets.
 #include <algorithm>
@@ -68,6 +71,7 @@ struct Options {
   bool inband = true;        // start / goal / tof follow the map on the wire
   float from_x = 0, from_y = 0, to_x = 0, to_y = 0;
   bool tof = false;
+  bool verify_follow = false;
   std::string fifo_in, fifo_out;
 };
 
@@ -103,6 +107,8 @@ int serve(Options opt, bool cell_planner, bool indirect) {
   planner.set_occupancy_threshold(1);
   planner.set_heuristic_multiplier((float)min_cost);
   planner.set_map(data, width, height);
+  // the dump after every step: follow the steps' deltas on the host instead of reading the whole field back each time
+  if (opt.tof && planner.map.follow_changes(true) != UFM_OK) throw std::runtime_error("follow_changes failed");
   planner.set_start(next_point);
   planner.set_goal(goal);
 
@@ -140,7 +146,16 @@ int serve(Options opt, bool cell_planner, bool indirect) {
 
     if (opt.tof) {          // every element that holds a value, as (x, y, g, rhs)
       io.put<int8_t>(4);
-      io.put<int64_t>((int64_t)planner.map.size());
+      const size_t held = planner.map.size();
+      if (opt.verify_follow) {
+        typename Planner::Map whole;
+        int nx = 0, ny = 0;
+        whole.attach(planner.native_handle());
+        if (ufm_field_dims(planner.native_handle(), &nx, &ny) != UFM_OK) throw std::runtime_error("ufm_field_dims failed");
+        whole.set_dims(nx, ny);
+        if (whole.size() != held || !(whole.buckets == planner.map.buckets)) throw std::runtime_error("the followed map differs from a read of the whole field");
+      }
+      io.put<int64_t>((int64_t)held);
       for (const auto &bucket : planner.map.buckets) {
         for (const auto &kv : bucket) {
           const Elem &el = kv.first;
@@ -170,7 +185,7 @@ int serve(Options opt, bool cell_planner, bool indirect) {
 
 void usage(const char *argv0) {
   std::fprintf(stderr,
-               "Usage:\n\t%s [--planner FD|SG|DFM] [--level K] [--max-moves N] <fifo_in> <fifo_out>\n"
+               "Usage:\n\t%s [--planner FD|SG|DFM] [--level K] [--max-moves N] [--verify-follow] <fifo_in> <fifo_out>\n"
                "\t%s [...] <mapfile> <from_x> <from_y> <to_x> <to_y> <cspace> <fifo_in> <fifo_out> <gui> <tof> <outpath>\n",
                argv0, argv0);
 }
@@ -199,6 +214,7 @@ int main(int argc, char **argv) {
     if (a == "--planner" && i + 1 < argc) opt.planner = argv[++i];
     else if (a == "--level" && i + 1 < argc) opt.level = std::atoi(argv[++i]);
     else if (a == "--max-moves" && i + 1 < argc) opt.max_moves = std::atol(argv[++i]);
+    else if (a == "--verify-follow") opt.verify_follow = true;
     else if (a == "-h" || a == "--help") { usage(argv[0]); return 0; }
     else pos.push_back(a);
   }

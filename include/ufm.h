@@ -193,6 +193,29 @@ int ufm_check_info(ufm_t *p, uint64_t out[6]);
 #define UFM_DFM_RTOL 2e-6f
 int ufm_read_queue(ufm_t *p, int cap, int32_t *xy, float *g_rhs, int *total);
 
+/* ---- step deltas: what changed since the caller last looked (no reference counterpart: the reference's drivers dump the whole
+ * ExpandedMap after every step, Tests/Planners/DFM/main.cpp:139-156; a consumer that follows the state over a mission applies these
+ * records to a host copy instead, at a cost proportional to the change).  OPT-IN: off by default, and off costs nothing -- no
+ * allocation, no launch.
+ * Baseline: ufm_track_changes(p, 1) gives every map a baseline -- the state the caller was last told -- and sets it to the reference's
+ * empty ExpandedMap: every element +inf, no Info.  The first read after a plan therefore returns every element that holds a value.
+ * ufm_set_map sets the baseline of its map to empty again; ufm_reset does not touch it (the next step's delta carries the removals);
+ * ufm_track_changes(p, 0) frees it.
+ * A record is written for every element whose value BITS differ from the baseline's and, for a level-1/2 planner, for every element
+ * whose Info differs: the stored back-pointer byte as ufm_read_info reports it (node planners: the node it names; MS-DFM: the pair it
+ * resolves to on the field and the raster as they stand, which can move with a neighbour's value).  xy: int32 [cap][2] element
+ * coordinates; g: float [cap], the value now -- +inf: the element no longer holds one (the reference's erased / (inf, inf) element);
+ * info: int32 [cap][2] in ufm_read_info's format, may be NULL, UFM_ERR_INVALID if non-NULL for a level-0 planner.  Order unspecified.
+ * RHS equals G, as for ufm_read_field.
+ * All or nothing: *total is always the full count.  total <= cap: all records are delivered and the baseline advances to the state as
+ * it stands.  total > cap (cap 0 with NULL buffers just counts): nothing is committed and nothing need be delivered -- the same delta
+ * is there at the next call; a caller never sees half a delta.
+ * A call between two steps with nothing changed returns total == 0; deltas accumulate over any number of steps between two reads;
+ * patches a batch holds back ("defer_patches") are applied first, as by ufm_read_queue.
+ * UFM_ERR_INVALID if tracking is off, no map is set, or the arguments are bad. ---- */
+int ufm_track_changes(ufm_t *p, int enable);
+int ufm_read_changes(ufm_t *p, int cap, int32_t *xy, float *g, int32_t *info, int *total);
+
 /* ---- path extraction: replaces LinearInterpolationPathExtractor::extract_path
  * (PathExtraction/LinearInterpolationPathExtractor_impl.h:11-58) and the traversal case tables it
  * calls (ProjectToolkit/InterpolatedTraversal.cpp).  Walks the RHS field from the start position
@@ -255,6 +278,9 @@ int ufm_batch_check_info(ufm_batch_t *b, uint64_t out[6]);                 /* as
 int ufm_batch_set_param(ufm_batch_t *b, const char *name, double value);   /* as ufm_set_param */
 int ufm_batch_set_profiling(ufm_batch_t *b, int enable);
 void *ufm_batch_stream(ufm_batch_t *b, int shard);                         /* hipStream_t of shard's engine */
+/* as ufm_track_changes / ufm_read_changes: tracking for every map of the batch, a read for map i alone (one scan of that map) */
+int ufm_batch_track_changes(ufm_batch_t *b, int enable);
+int ufm_batch_read_changes(ufm_batch_t *b, int i, int cap, int32_t *xy, float *g, int32_t *info, int *total);
 /* all maps in one launch: path_xy [n_maps][cap_points][2], step_costs [n_maps][cap_costs], info [n_maps] */
 int ufm_batch_extract_path(ufm_batch_t *b, int max_steps, int lookahead, int allow_indirect,
                            float *path_xy, int cap_points, float *step_costs, int cap_costs, ufm_path_info *info);

@@ -24,6 +24,7 @@ SYMBOLS = [
     "ufm_check_layout", "ufm_batch_check_layout", "ufm_batch_set_param", "ufm_check_info", "ufm_batch_check_info",
     "ufm_batch_create_sharded", "ufm_batch_shards", "ufm_batch_set_heuristic_multiplier", "ufm_batch_set_map_device",
     "ufm_batch_patch_map_device", "ufm_batch_read_map", "ufm_batch_set_profiling", "ufm_batch_stream", "ufm_read_queue",
+    "ufm_track_changes", "ufm_read_changes", "ufm_batch_track_changes", "ufm_batch_read_changes",
 ]
 
 
@@ -152,6 +153,10 @@ def load_library():
     L.ufm_read_info_derived.argtypes = [vp, i, i, i, i, vp]
     L.ufm_extract_path.argtypes = [vp, i, i, i, vp, i, vp, i, C.POINTER(PathInfo)]
     L.ufm_batch_extract_path.argtypes = [vp, i, i, i, vp, i, vp, i, C.POINTER(PathInfo)]
+    L.ufm_track_changes.argtypes = [vp, i]
+    L.ufm_read_changes.argtypes = [vp, i, vp, vp, vp, vp]
+    L.ufm_batch_track_changes.argtypes = [vp, i]
+    L.ufm_batch_read_changes.argtypes = [vp, i, i, vp, vp, vp, vp]
     _LIB = L
     return L
 
@@ -159,6 +164,24 @@ def load_library():
 def _chk(rc, what):
     if rc != 0:
         raise UfmError("%s failed with code %d" % (what, rc))
+
+
+def _read_changes(call, what, want_info, cap=None):
+    """ufm_read_changes / ufm_batch_read_changes through `call(cap, xy, g, info, total)`: a counting call sizes the buffers (cap None),
+    the second call delivers.  Returns (xy int32 [n, 2], g float32 [n], info int32 [n, 2] | None, total); with an explicit cap that is
+    too small n = 0 and nothing was committed."""
+    total = C.c_int(0)
+    if cap is None:
+        _chk(call(0, None, None, None, C.addressof(total)), what)
+        cap = total.value
+        if cap == 0:
+            return np.zeros((0, 2), np.int32), np.zeros(0, np.float32), (np.zeros((0, 2), np.int32) if want_info else None), 0
+    xy = np.zeros((max(cap, 1), 2), np.int32)
+    g = np.zeros(max(cap, 1), np.float32)
+    info = np.zeros((max(cap, 1), 2), np.int32) if want_info else None
+    _chk(call(cap, xy.ctypes.data, g.ctypes.data, info.ctypes.data if want_info else None, C.addressof(total)), what)
+    n = total.value if total.value <= cap else 0
+    return xy[:n], g[:n], (info[:n] if want_info else None), total.value
 
 
 class Planner:
@@ -324,6 +347,18 @@ class Planner:
         n = min(total.value, cap)
         return xy[:n], gr[:n, 0].copy(), gr[:n, 1].copy(), total.value
 
+    def track_changes(self, on=True):
+        """step deltas (ufm_track_changes): the engine keeps a baseline -- what read_changes last delivered, empty at first"""
+        _chk(self.L.ufm_track_changes(self.h, int(on)), "ufm_track_changes")
+
+    def read_changes(self, want_info=False, cap=None):
+        """the elements whose value (want_info: or Info pair) differs from the baseline, all or nothing:
+        (xy int32 [n, 2], g float32 [n] -- +inf: the element lost its value --, info int32 [n, 2] | None); the baseline advances.
+        cap: deliver only if the delta has at most that many records; then returns (xy, g, info, total) -- n = 0 and nothing
+        committed if total > cap"""
+        out = _read_changes(lambda *a: self.L.ufm_read_changes(self.h, *a), "ufm_read_changes", want_info, cap)
+        return out if cap is not None else out[:3]
+
 
 class BatchPlanner:
     """Batch of independent, equally sized map instances: on one device, or (devices=[...]) spread over several
@@ -432,6 +467,15 @@ class BatchPlanner:
 
     def set_param(self, name, value):
         _chk(self.L.ufm_batch_set_param(self.h, name.encode(), float(value)), "ufm_batch_set_param")
+
+    def track_changes(self, on=True):
+        """as Planner.track_changes, for every map"""
+        _chk(self.L.ufm_batch_track_changes(self.h, int(on)), "ufm_batch_track_changes")
+
+    def read_changes(self, i, want_info=False, cap=None):
+        """as Planner.read_changes, for map i"""
+        out = _read_changes(lambda *a: self.L.ufm_batch_read_changes(self.h, i, *a), "ufm_batch_read_changes", want_info, cap)
+        return out if cap is not None else out[:3]
 
     def check_info(self):
         """as Planner.check_info, summed over the maps"""

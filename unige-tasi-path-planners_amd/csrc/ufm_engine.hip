@@ -47,6 +47,7 @@ namespace {
 #include "ufm_region.h"
 
 #include "ufm_host.h"
+#include "ufm_delta.h"
 
 }  // namespace
 
@@ -416,6 +417,16 @@ void *ufm_batch_stream(ufm_batch_t *b, int shard) { return (b && shard >= 0 && s
 int ufm_read_info(ufm_t *p, int x0, int y0, int nx, int ny, int32_t *info) { return p ? engine_read_info(p->e, 0, x0, y0, nx, ny, info, false) : UFM_ERR_INVALID; }
 int ufm_read_info_derived(ufm_t *p, int x0, int y0, int nx, int ny, int32_t *info) { return p ? engine_read_info(p->e, 0, x0, y0, nx, ny, info, true) : UFM_ERR_INVALID; }
 int ufm_read_queue(ufm_t *p, int cap, int32_t *xy, float *g_rhs, int *total) { return p ? engine_read_queue(p->e, 0, cap, xy, g_rhs, total) : UFM_ERR_INVALID; }
+int ufm_track_changes(ufm_t *p, int enable) { return p ? engine_track_changes(p->e, enable) : UFM_ERR_INVALID; }
+int ufm_read_changes(ufm_t *p, int cap, int32_t *xy, float *g, int32_t *info, int *total) { return p ? engine_read_changes(p->e, 0, cap, xy, g, info, total) : UFM_ERR_INVALID; }
+int ufm_batch_track_changes(ufm_batch_t *b, int enable) {
+    if (!b) return UFM_ERR_INVALID;
+    for (Engine *e : b->shards) { const int rc = engine_track_changes(e, enable); if (rc != UFM_OK) return rc; }
+    return UFM_OK;
+}
+int ufm_batch_read_changes(ufm_batch_t *b, int i, int cap, int32_t *xy, float *g, int32_t *info, int *total) { UFM_BATCH_MAP(b, i); return engine_read_changes(e, li, cap, xy, g, info, total); }
+// profiling: duration of the last scan kernel of ufm_read_changes (tools/delta_probe.py; not part of include/ufm.h)
+int ufm_debug_delta_ms(ufm_t *p, float *ms) { if (!p || !ms) return UFM_ERR_INVALID; *ms = p->e->trk_scan_ms; return UFM_OK; }
 int ufm_extract_path(ufm_t *p, int max_steps, int lookahead, int allow_indirect,
                      float *path_xy, int cap_points, float *step_costs, int cap_costs, ufm_path_info *info) {
     return p ? engine_extract_path(p->e, max_steps, lookahead, allow_indirect, path_xy, cap_points, step_costs, cap_costs, info) : UFM_ERR_INVALID;

@@ -176,12 +176,25 @@ struct Engine {
     int flush_lazy();
     int ensure_pmask(size_t n);
     bool region_fits(const int (*rects)[5], int nrect, int m, int *tx0, int *ntx, int *ty0, int *nty) const;
+    // step deltas (ufm_track_changes / ufm_read_changes, ufm_delta.h): nothing below exists unless a caller turned tracking on
+    bool track = false;
+    float *trk_g = nullptr;          // the baseline: the field as the caller was last told, in the layout of P.G (same gstride)
+    uint8_t *trk_key = nullptr;      // ... and (level 1/2) the key of every element's Info pair (info_from_byte, ufm_path.h)
+    void *trk_rec = nullptr;         // record buffer of the scan (DeltaRecords)
+    size_t trk_cap = 0;              // (records)
+    hipEvent_t trk_ev[2] = {nullptr, nullptr};
+    float trk_scan_ms = 0.0f;        // profiling: duration of the last scan kernel
+    int track_alloc();
+    int track_reset(int m);
+    int track_records(size_t cap);
+    void track_free();
     bool lazy_region_ok() const;
 };
 
 void Engine::release() {
     if (!allocated) return;
     if (stream) hipStreamSynchronize(stream);
+    track_free();
     drop_graphs();                       // captured kernel arguments hold these pointers
     deferred.clear();
     std::memset(&graph_sig, 0, sizeof(graph_sig));
@@ -295,6 +308,7 @@ int Engine::alloc(int width, int length) {
         return UFM_OK;
     }();
     if (rc != UFM_OK) { release(); return rc; }
+    if (track) { rc = track_alloc(); if (rc != UFM_OK) { release(); return rc; } }
     pending.clear();
     for (auto &ms : maps) { ms.have_map = false; ms.initialize_search = true; }
     return UFM_OK;
@@ -1296,6 +1310,7 @@ int engine_destroy(Engine *e) {
     for (hipEvent_t v : e->ev) hipEventDestroy(v);
     for (hipEvent_t v : e->own_ev) if (v) hipEventDestroy(v);
     for (hipEvent_t v : e->reg_ev) if (v) hipEventDestroy(v);
+    for (hipEvent_t v : e->trk_ev) if (v) hipEventDestroy(v);
     if (e->d_patch) hipFree(e->d_patch);
     if (e->d_pmask) hipFree(e->d_pmask);
     if (e->d_field) hipFree(e->d_field);
@@ -1340,6 +1355,7 @@ int engine_set_map(Engine *e, int m, const uint8_t *src, bool on_device, int wid
         HIPCHK(hipStreamSynchronize(e->stream));
         if (h_acc[1] > 0) e->mean_cost = (float)((double)h_acc[0] / (double)h_acc[1]);
     }
+    if (e->track) { int rc = e->track_reset(m); if (rc != UFM_OK) return rc; }   // a new raster: the caller's view of this map starts empty again
     e->maps[m].have_map = true;   // initialize_graph = false, ReplannerBase.h:87
     // goal element validity depends on the map size
     MapState &ms = e->maps[m];

@@ -425,16 +425,16 @@ __device__ float dfm_stencil(int ca, int cb, float ga, float gb, float tau, floa
 // MS-DFM level 1, code (q << 1) | w: the candidate of min_rhs_decreased_neighbor (impl:270-313) built on the neighbour w of axis q (vertical,
 // horizontal, TR-BL, TL-BR) and the cell of the perpendicular pair that bit 5 names (1: +po of QuadConsts<ALGO_DFM1>; written as best_cell picks it,
 // impl:284-296); out = the pair compute_optimal_cost leaves (impl:322-342).
-__global__ void k_info_stored(PathField F, const uint8_t *bp, int x0, int y0, int nx, int ny, int32_t *out) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= nx * ny) return;
-    const int x = x0 + e / ny, y = y0 + e % ny;
-    int b0 = -1, b1 = -1;
-    const int code = bp[((size_t)(x / T) * F.TY + (y / T)) * (T * T) + (size_t)(x % T) * T + (y % T)];
+// (info_from_byte: the pair for one element whose value is g; returns what of the byte and of the field around the element the pair depends on, as one
+// byte -- node planners: the code; MS-DFM: the cell(s) compute_optimal_cost leaves, in their order, as directions from the element;
+// 0xFF: no pair -- so that two equal returns mean two equal pairs: the change scan compares it, ufm_delta.h)
+__device__ __forceinline__ int info_from_byte(const PathField &F, int code, float g, int x, int y, int &b0, int &b1) {
+    b0 = -1; b1 = -1;
+    int key = 0xFF;
 #ifdef UFM_BPDEBUG
-    if (code == 0xFD) { out[2 * e] = -3; out[2 * e + 1] = -3; return; }
+    if (code == 0xFD) { b0 = -3; b1 = -3; return 0xFD; }
 #endif
-    if (code != 0xFF && field_at(F, x, y) < INFINITY) {
+    if (code != 0xFF && g < INFINITY) {
         const int q = (code >> 3) & 3, w = (code >> 2) & 1;      // the byte: (((q << 1) | w) << 2) | dep
         if (F.cells) {
             const int NX[4][2] = {{-1, 1}, {0, 0}, {-1, 1}, {-1, 1}}, NY[4][2] = {{0, 0}, {-1, 1}, {1, -1}, {-1, 1}};
@@ -444,7 +444,11 @@ __global__ void k_info_stored(PathField F, const uint8_t *bp, int x0, int y0, in
             const int px = x + ps * POX[q], py = y + ps * POY[q];
             const float gp = field_at(F, px, py);
             auto lin = [&](int ax, int ay) { return elem_ok(F, ax, ay) ? ax * F.EY + ay : -2; };
-            dfm_stencil(lin(qx, qy), lin(px, py), field_at(F, qx, qy), gp, raster_cost(F, x, y), q < 2 ? 1.0f : PATH_SQRT2, b0, b1);
+            const int la = lin(qx, qy);
+            dfm_stencil(la, lin(px, py), field_at(F, qx, qy), gp, raster_cost(F, x, y), q < 2 ? 1.0f : PATH_SQRT2, b0, b1);
+            // (the pair itself, as directions from the element: two candidates can leave the same two cells)
+            const int da = (qx - x + 1) * 3 + (qy - y + 1), dp = (px - x + 1) * 3 + (py - y + 1);
+            if (b0 != -1) key = (b0 == la ? da : dp) | ((b1 == -1 ? 15 : (b0 == la ? dp : da)) << 4);
         } else {
             const int dx = (q & 2) ? 1 : -1, dy = (q & 1) ? 1 : -1;
             const int p1x = w ? x : x + dx, p1y = w ? y + dy : y, p2x = x + dx, p2y = y + dy;
@@ -452,8 +456,18 @@ __global__ void k_info_stored(PathField F, const uint8_t *bp, int x0, int y0, in
             ring_at(ring_of(p1x - x, p1y - y) + 1, cx, cy);
             const bool p1_first = (x + cx == p2x) && (y + cy == p2y);
             b0 = p1_first ? p1x * F.EY + p1y : p2x * F.EY + p2y;
+            key = (code >> 2) & 7;
         }
     }
+    return key;
+}
+__global__ void k_info_stored(PathField F, const uint8_t *bp, int x0, int y0, int nx, int ny, int32_t *out) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= nx * ny) return;
+    const int x = x0 + e / ny, y = y0 + e % ny;
+    int b0, b1;
+    const int code = bp[((size_t)(x / T) * F.TY + (y / T)) * (T * T) + (size_t)(x % T) * T + (y % T)];
+    info_from_byte(F, code, field_at(F, x, y), x, y, b0, b1);
     out[2 * e] = b0;
     out[2 * e + 1] = b1;
 }

@@ -150,6 +150,15 @@ class Pipes:
             raise EOFError("planner closed the pipe")
         return b
 
+    def receive_expanded(self):
+        """message 4, the `tof` dump a planner sends after every step (Tests/Planners/*/main.cpp:139-156): every element that holds
+        a value, as a structured array (x, y int32; g, rhs float32)"""
+        code = self.recv("b")
+        if code != (4,):
+            raise ValueError("expected message 4, got %r" % (code,))
+        (count,) = self.recv("q")
+        return np.frombuffer(self.recv_bytes(16 * count), dtype=[("x", "<i4"), ("y", "<i4"), ("g", "<f4"), ("rhs", "<f4")])
+
     def close(self):
         self.o.close()
         self.i.close()
@@ -157,7 +166,7 @@ class Pipes:
 
 def run_mission(cmd, pipe_to_planner, pipe_from_planner, img_h, start, goal, radius=5, cspace_diameter=1,
                 low_res_penalty=10, use_heuristic=False, max_moves=10000, on_map=None, on_move=None, display_shift=0.0,
-                append_pipes=True):
+                append_pipes=True, tof=False, on_expanded=None):
     """One mission as Tests/run_test.py:85-177 runs it: launch the planner process `cmd`, send the
     C-space of the low-resolution map, then per robot position reveal the disc of radius `radius`,
     send its bounding patch and the heuristic hint, receive the planned path.  start / goal are
@@ -165,7 +174,8 @@ def run_mission(cmd, pipe_to_planner, pipe_from_planner, img_h, start, goal, rad
     form ignores nothing because none is sent then -- pass start=None).
     on_map(cspace, min_cost) is called with what the planner receives first;
     on_move(i, position, top, left, patch, min_cost, (path, costs, dist, cost, times)) after every reply
-    (position without `display_shift`, the half cell the DFM driver adds for display).  Returns the list of positions visited and whether the planner reported the end."""
+    (position without `display_shift`, the half cell the DFM driver adds for display); with tof the planner is asked for its dump of the
+    expanded elements after every step and on_expanded(i, records) gets it (Pipes.receive_expanded).  Returns the list of positions visited and whether the planner reported the end."""
     for p in (pipe_to_planner, pipe_from_planner):
         if not os.path.exists(p):
             os.mkfifo(p)
@@ -185,7 +195,7 @@ def run_mission(cmd, pipe_to_planner, pipe_from_planner, img_h, start, goal, rad
         io.send("ii", width, height)
         io.send_bytes(np.ascontiguousarray(cspace).tobytes())
         if start is not None:
-            io.send("ffffB", float(start[0]), float(start[1]), float(goal[0]), float(goal[1]), 0)
+            io.send("ffffB", float(start[0]), float(start[1]), float(goal[0]), float(goal[1]), 1 if tof else 0)
         io.send("i", min_cost)
         io.flush()
         if on_map is not None:
@@ -222,6 +232,10 @@ def run_mission(cmd, pipe_to_planner, pipe_from_planner, img_h, start, goal, rad
             times = io.recv("fff")
             if on_move is not None:
                 on_move(len(trace) - 1, (x, y), top, left, patch, min_cost, (path, costs, dist, cost, times))
+            if tof:
+                records = io.receive_expanded()
+                if on_expanded is not None:
+                    on_expanded(len(trace) - 1, records)
         io.send("b", 2)
         io.flush()
         if finished:

@@ -49,6 +49,10 @@ class ReplannerBase {
     map.invalidate();
     priority_queue.invalidate();
     if (rc != UFM_OK) { last_error = rc; return rc; }
+    if (map.following()) {        // opt-in (map.follow_changes): the host copy takes the step's delta
+      const int rd = map.apply_changes();
+      if (rd != UFM_OK) { last_error = rd; return rd; }
+    }
     u_time = st.u_ms; p_time = st.p_ms;
     num_nodes_updated = st.updated; num_nodes_expanded = st.expanded;
     stats = st;
