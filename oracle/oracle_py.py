@@ -30,6 +30,39 @@ def case_counts_reset():
     lib().orc_case_counts_reset()
 
 
+PC_KINDS = ("corner", "contiguous", "opposite")
+PC_TYPES = ("I", "II", "III", "A", "B")
+PC_ORIENT = ("h", "v")     # p0 and p1 share y / share x (the case functions' "p lies on a vertical edge")
+_PC_CHOSEN, _PC_WON, _PC_RV, _PC_RX, _PC_RY, _PC_MOVES, _PC_N = 0, 30, 60, 68, 74, 80, 85      # ufm_oracle.h: ORC_PC_*
+PC_LOG_W = 8
+
+
+def path_census_reset():
+    lib().orc_path_census_reset()
+
+
+def path_census():
+    """the extractor's census since the last reset (ufm_oracle.h: orc_path_census): dict with 'chosen' / 'won' keyed by
+    (kind, type, orientation), 'ring' keyed by 'vertex' / 'xfrac' / 'yfrac' (lists per slot) and the scalar counters"""
+    a = (C.c_ulong * _PC_N)()
+    lib().orc_path_census(a)
+    a = list(a)
+    keys = [(k, t, o) for k in PC_KINDS for t in PC_TYPES for o in PC_ORIENT]
+    return {"chosen": dict(zip(keys, a[_PC_CHOSEN:_PC_WON])), "won": dict(zip(keys, a[_PC_WON:_PC_RV])),
+            "ring": {"vertex": a[_PC_RV:_PC_RX], "xfrac": a[_PC_RX:_PC_RY], "yfrac": a[_PC_RY:_PC_MOVES]},
+            "moves": a[_PC_MOVES], "la_rejected_any": a[_PC_MOVES + 1], "la_rejected_winner": a[_PC_MOVES + 2],
+            "tie_break": a[_PC_MOVES + 3], "stuck_after_move": a[_PC_MOVES + 4]}
+
+
+def path_move_log():
+    """the moves of the last extraction: int array [moves, 8] = way points, step costs, kind, type, orientation (-1: stayed put), ring,
+    winning slot, flags (ufm_oracle.h: orc_path_move_log)"""
+    n = lib().orc_path_move_log(None, 0)
+    out = np.zeros((max(n, 1), PC_LOG_W), np.int32)
+    lib().orc_path_move_log(out.ctypes.data, n)
+    return out[:min(n, 4096)]
+
+
 def build():
     subprocess.check_call(["make", "-s", "-C", _HERE])
 
@@ -78,6 +111,9 @@ def lib():
         L.orc_min_rhs_info.restype = f
         L.orc_min_rhs_info.argtypes = [vp, i, i, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         L.orc_load_g.argtypes = [vp, vp]
+        L.orc_path_census.argtypes = [C.POINTER(C.c_ulong)]
+        L.orc_path_move_log.restype = i
+        L.orc_path_move_log.argtypes = [vp, i]
         L.orc_cost_via.restype = f
         L.orc_cost_via.argtypes = [vp, i, i, i, i, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         _LIB = L

@@ -102,6 +102,27 @@ int orc_extract_path(const orc_t *p, int lookahead, int max_steps, int allow_ind
                      float *path_xy, int cap_pts, float *costs, int cap_costs,
                      int *n_costs, float *total_cost, float *total_dist);
 int orc_threshold_uchar(const orc_t *p);
+/* Census of the extractor (counters only: no result of an extraction depends on them), process-wide, since the last reset.
+ * Case index = (kind * 5 + type) * 2 + orientation; kind: 0 corner, 1 contiguous edge, 2 opposite edge; type: 0 I, 1 II, 2 III, 3 A, 4 B;
+ * orientation: 0 = p0 and p1 share y (the case functions' "horizontal" branch), 1 = they share x ("p lies on a vertical edge").
+ *   CHOSEN[30]            the case was chosen for a primary edge's candidate (lookahead evaluations are not counted)
+ *   WON[30]               ... and that candidate became the move
+ *   RING_VERTEX[8]        ring slot (Graph::consecutive_neighbors order) of the first node of the winning edge, position on a vertex
+ *   RING_XFRAC[6] / RING_YFRAC[6]   the same for a position with a fractional x / y (the two 6-node rings)
+ *   MOVES                 calls of getPathAdditions by the walk
+ *   LA_REJECTED_ANY       moves in which the lookahead test rejected at least one candidate
+ *   LA_REJECTED_WINNER    moves in which it rejected the candidate that would otherwise have won (first minimum over all candidates)
+ *   TIE_BREAK             moves whose winner's cost_to_goal a later usable candidate equalled (ring order decided)
+ *   STUCK_AFTER_MOVE      moves without a usable edge after at least one real move of the same walk (the previous step_cost is added again) */
+enum { ORC_PC_CHOSEN = 0, ORC_PC_WON = 30, ORC_PC_RING_VERTEX = 60, ORC_PC_RING_XFRAC = 68, ORC_PC_RING_YFRAC = 74, ORC_PC_MOVES = 80,
+       ORC_PC_LA_REJECTED_ANY, ORC_PC_LA_REJECTED_WINNER, ORC_PC_TIE_BREAK, ORC_PC_STUCK_AFTER_MOVE, ORC_PC_N };
+void orc_path_census(unsigned long *out /* [ORC_PC_N] */);
+void orc_path_census_reset(void);
+/* The moves of the last extraction, in order: per move ORC_PC_LOG_W ints -- way points, step costs, kind, type, orientation (-1: stayed put),
+ * ring (0 vertex, 1 x fractional, 2 y fractional), winning slot (-1: none), flags (1 lookahead rejected a candidate, 2 ... the would-be
+ * winner, 4 tie-break).  Returns the number of moves the walk made (the first min(that, ORC_PC_LOG_CAP, cap_moves) are written). */
+enum { ORC_PC_LOG_W = 8, ORC_PC_LOG_CAP = 4096 };
+int orc_path_move_log(int *out, int cap_moves);
 /* back-pointer(s) min_rhs<1/2> derives from the current G field (a pure function of it), and a
  * test hook that loads a G field */
 float orc_min_rhs_info(const orc_t *p, int x, int y, int32_t *b0, int32_t *b1);

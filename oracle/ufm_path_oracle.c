@@ -39,6 +39,7 @@ typedef struct {
     float costs[2];
     int ns, nc;
     float cost_to_goal;
+    int kind, type, vert;   /* census only: which case function made it (tt_emit); never read by the extractor */
 } padd;
 
 typedef struct {
@@ -52,6 +53,20 @@ typedef struct {
 
 enum { K_CORNER = 0, K_CONTIG = 1, K_OPP = 2 };
 enum { T_I = 0, T_II = 1, T_III = 2, T_A = 3, T_B = 4 };
+
+/* ---- census (ufm_oracle.h: orc_path_census) -- counters only, process-wide like orc_case_counts; nothing below reads them back ---- */
+static unsigned long pc[ORC_PC_N];
+static int pc_log[ORC_PC_LOG_CAP][ORC_PC_LOG_W], pc_log_n;
+void orc_path_census_reset(void) { for (int i = 0; i < ORC_PC_N; ++i) pc[i] = 0; pc_log_n = 0; }
+void orc_path_census(unsigned long *out) { for (int i = 0; i < ORC_PC_N; ++i) out[i] = pc[i]; }
+int orc_path_move_log(int *out, int cap_moves) {
+    const int n = pc_log_n < ORC_PC_LOG_CAP ? pc_log_n : ORC_PC_LOG_CAP;
+    for (int i = 0; i < n && i < cap_moves; ++i) for (int k = 0; k < ORC_PC_LOG_W; ++k) out[i * ORC_PC_LOG_W + k] = pc_log[i][k];
+    return pc_log_n;
+}
+static inline int pc_case(int kind, int type, int vert) { return (kind * 5 + type) * 2 + (vert ? 1 : 0); }
+/* what the last top-level path_additions() decided, for the move log of orc_extract_path_field */
+static struct { int slot, ring, la_any, la_winner, tie; } pc_last;
 
 /* Macros.h:9-12,18,24 */
 static inline float sq(float x) { return x * x; }
@@ -95,22 +110,22 @@ static int p_valid_vertex(const pctx *c, pos_t p) {
 
 /* Graph.cpp:151-200 consecutive_neighbors(Position): ring of 6 (point on an edge) or 8 nodes,
  * pairs of consecutive valid nodes; a valid node followed by an invalid one skips a slot */
-static int p_edges(const pctx *c, pos_t p, nd_t ea[8], nd_t eb[8]) {
+static int p_edges(const pctx *c, pos_t p, nd_t ea[8], nd_t eb[8], int slot[8], int *ring) {
     float ipx, ipy;
     const float dx = modff(p.x, &ipx), dy = modff(p.y, &ipy);
     const int X = (int)ipx, Y = (int)ipy;
     nd_t r[8];
     int n;
     if (0.0f < dx && dx < 1.0f) {
-        n = 6;
+        n = 6; *ring = 1;
         r[0] = (nd_t){X, Y}; r[1] = (nd_t){X, Y - 1}; r[2] = (nd_t){X + 1, Y - 1};
         r[3] = (nd_t){X + 1, Y}; r[4] = (nd_t){X + 1, Y + 1}; r[5] = (nd_t){X, Y + 1};
     } else if (0.0f < dy && dy < 1.0f) {
-        n = 6;
+        n = 6; *ring = 2;
         r[0] = (nd_t){X, Y}; r[1] = (nd_t){X + 1, Y}; r[2] = (nd_t){X + 1, Y + 1};
         r[3] = (nd_t){X, Y + 1}; r[4] = (nd_t){X - 1, Y + 1}; r[5] = (nd_t){X - 1, Y};
     } else {
-        n = 8;
+        n = 8; *ring = 0;
         r[0] = (nd_t){X + 1, Y}; r[1] = (nd_t){X + 1, Y + 1}; r[2] = (nd_t){X, Y + 1}; r[3] = (nd_t){X - 1, Y + 1};
         r[4] = (nd_t){X - 1, Y}; r[5] = (nd_t){X - 1, Y - 1}; r[6] = (nd_t){X, Y - 1}; r[7] = (nd_t){X + 1, Y - 1};
     }
@@ -118,7 +133,7 @@ static int p_edges(const pctx *c, pos_t p, nd_t ea[8], nd_t eb[8]) {
     for (int i = 0; i < n; ++i) {
         if (p_valid_node(c, r[i].x, r[i].y)) {
             const nd_t nxt = r[(i + 1) % n];
-            if (p_valid_node(c, nxt.x, nxt.y)) { ea[m] = r[i]; eb[m] = nxt; ++m; }
+            if (p_valid_node(c, nxt.x, nxt.y)) { ea[m] = r[i]; eb[m] = nxt; slot[m] = i; ++m; }
             else ++i;
         }
     }
@@ -193,6 +208,7 @@ static float tt_condcost(int kind, int type, const tparams *t) {
 static void tt_emit(int kind, int type, const tparams *t, padd *o) {
     const int vert = (t->p0.x == (float)t->p1.x); /* "p lies on a vertical edge" */
     o->ns = o->nc = 0;
+    o->kind = kind; o->type = type; o->vert = vert;
     switch (type) {
     case T_I: {
         if (kind == K_CORNER) {                                                      /* :12-41 */
@@ -420,16 +436,24 @@ static padd from_edge(const pctx *c, pos_t p, nd_t a, nd_t b, float *step_cost) 
 
 /* :165-213 getPathAdditions. A position without any usable edge returns the value-initialised
  * additions (no steps, cost_to_goal 0) and leaves step_cost untouched, as the reference does. */
+static int pc_depth;   /* census: 0 in the walk's own call, 1 inside a lookahead */
 static padd path_additions(const pctx *c, pos_t p, int do_lookahead, float *step_cost) {
     float min_cost = INFINITY;
     padd best = {0};
     nd_t ea[8], eb[8];
-    const int ne = p_edges(c, p, ea, eb);
+    int slot[8], ring = 0;
+    const int ne = p_edges(c, p, ea, eb, slot, &ring);
     const int vertex = p_valid_vertex(c, p);
+    /* census (top level only, depth 0): the winner's edge, the candidate that would win without the lookahead test, rejections, ties */
+    const int top = (pc_depth == 0);
+    int win_e = -1, alt_e = -1, n_rej = 0, n_tie = 0, rej[8] = {0};
+    float alt_min = INFINITY;
+    ++pc_depth;
     for (int e = 0; e < ne; ++e) {
         float cur = INFINITY;
         padd t = vertex ? from_corner(c, p, ea[e], eb[e], &cur) : from_edge(c, p, ea[e], eb[e], &cur);
         if (t.ns == 0) continue;
+        if (top) { ++pc[ORC_PC_CHOSEN + pc_case(t.kind, t.type, t.vert)]; if (t.cost_to_goal < alt_min) { alt_min = t.cost_to_goal; alt_e = e; } }
         float la = -1.0f;
         if (do_lookahead && !p_valid_vertex(c, t.steps[t.ns - 1])) {
             float dummy = 0.0f;
@@ -440,11 +464,26 @@ static padd path_additions(const pctx *c, pos_t p, int do_lookahead, float *step
                 p.x, p.y, e, ea[e].x, ea[e].y, eb[e].x, eb[e].y, t.ns, t.steps[t.ns - 1].x, t.steps[t.ns - 1].y, t.cost_to_goal, cur, la,
                 (la > t.cost_to_goal) ? " REJECTED" : (t.cost_to_goal < min_cost ? " best" : (t.cost_to_goal == min_cost ? " TIE" : "")));
 #endif
-        if (la > t.cost_to_goal) continue;
+        if (la > t.cost_to_goal) { rej[e] = 1; ++n_rej; continue; }
+        if (top && t.cost_to_goal == min_cost && min_cost < INFINITY) ++n_tie;   /* an equal, later candidate: ring order keeps the earlier one */
         if (t.cost_to_goal < min_cost) {
             min_cost = t.cost_to_goal;
             best = t;
             *step_cost = cur;
+            win_e = e; n_tie = 0;
+        }
+    }
+    --pc_depth;
+    if (top) {
+        ++pc[ORC_PC_MOVES];
+        pc_last.slot = -1; pc_last.ring = ring; pc_last.la_any = n_rej > 0; pc_last.tie = 0; pc_last.la_winner = 0;
+        if (n_rej > 0) ++pc[ORC_PC_LA_REJECTED_ANY];
+        if (alt_e >= 0 && rej[alt_e]) { ++pc[ORC_PC_LA_REJECTED_WINNER]; pc_last.la_winner = 1; }
+        if (win_e >= 0) {
+            ++pc[ORC_PC_WON + pc_case(best.kind, best.type, best.vert)];
+            ++pc[(ring == 0 ? ORC_PC_RING_VERTEX : ring == 1 ? ORC_PC_RING_XFRAC : ORC_PC_RING_YFRAC) + slot[win_e]];
+            pc_last.slot = slot[win_e];
+            if (n_tie > 0) { ++pc[ORC_PC_TIE_BREAK]; pc_last.tie = 1; }
         }
     }
     return best;
@@ -462,10 +501,19 @@ int orc_extract_path_field(const float *rhs, int nx, int ny, int cells,
     int npts = 0, ncost = 0, curr_step = 0;
     float tcost = 0, tdist = 0, min_cost, step_cost = 0.0f;
     pos_t last = c.start;
+    int real_moves = 0;   /* census */
+    pc_log_n = 0;
     if (npts < cap_pts) { path_xy[2 * npts] = last.x; path_xy[2 * npts + 1] = last.y; }
     ++npts;
     do {
         padd pa = path_additions(&c, last, lookahead, &step_cost);
+        if (pa.ns > 0) ++real_moves; else if (real_moves > 0) ++pc[ORC_PC_STUCK_AFTER_MOVE];
+        if (pc_log_n < ORC_PC_LOG_CAP) {
+            int *g = pc_log[pc_log_n];
+            g[0] = pa.ns; g[1] = pa.nc; g[2] = pa.ns ? pa.kind : -1; g[3] = pa.ns ? pa.type : -1; g[4] = pa.ns ? pa.vert : -1;
+            g[5] = pc_last.ring; g[6] = pc_last.slot; g[7] = pc_last.la_any | (pc_last.la_winner << 1) | (pc_last.tie << 2);
+        }
+        ++pc_log_n;
         float step_dist = 0;
         pos_t prev = last;
         for (int i = 0; i < pa.ns; ++i) {
