@@ -36,6 +36,39 @@ def test_library_exports_every_symbol():
         assert hasattr(lib, name), name
 
 
+def test_only_the_committed_build_switches_remain():
+    """the preprocessor tests no UFM_* name in csrc/ but the switches something committed builds (csrc/ufm_defs.h lists them): the kernel text
+    is the kernel that runs"""
+    kept = {"UFM_TILE", "UFM_TIMING", "UFM_SWEEPSTAT", "UFM_STRICT_FENCES", "UFM_REGION_NG0"}
+    csrc = os.path.join(os.path.dirname(ufm_amd.library_path()), "csrc")
+    tested = {}
+    for f in sorted(os.listdir(csrc)):
+        for n, line in enumerate(open(os.path.join(csrc, f)), 1):
+            if re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b", line):
+                for name in re.findall(r"\bUFM_[A-Z0-9_]+", line):
+                    tested.setdefault(name, "%s:%d" % (f, n))
+    assert len(tested) >= 4, tested                      # (the scan does find the sites)
+    assert set(tested) <= kept, {k: v for k, v in tested.items() if k not in kept}
+
+
+def test_removed_experiments_are_not_exported():
+    """the arrival-order gating experiment left the product (tools/experiments/r4_dag_gating.diff): no debug entry point ..."""
+    if not os.path.exists(ufm_amd.library_path()):
+        ufm_amd.build_library()
+    lib = ctypes.CDLL(ufm_amd.library_path())
+    assert not hasattr(lib, "ufm_debug_set_tile_order")
+    # ... and, where a planner can be created, no run-time knob
+    try:
+        p = ufm_amd.Planner(ufm_amd.ALGO_FD, 0)
+    except ufm_amd.UfmError:
+        return
+    try:
+        assert p.L.ufm_set_param(p.h, b"dag", 1.0) == -22          # UFM_ERR_INVALID
+        assert p.L.ufm_set_param(p.h, b"owned_flags", 0.0) == 0    # (a name that exists is accepted)
+    finally:
+        p.close()
+
+
 def test_no_cpu_fallback():
     """Without a GPU creating a planner must fail loudly (negative code -> UfmError), never fall
     back to a CPU path.  With a GPU it simply succeeds."""

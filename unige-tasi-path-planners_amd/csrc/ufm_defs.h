@@ -1,8 +1,15 @@
-// ufm_defs.h -- compile-time knobs, the HBM layout (DevParams), the tile queues of the launch chain and of the resident kernel, diagnostics
+// ufm_defs.h -- build switches and tuned constants, the HBM layout (DevParams), the tile queues of the launch chain and of the resident kernel, diagnostics
 // (a piece of ufm_engine.hip, the engine's one translation unit: included there, inside its anonymous namespace)
 #pragma once
 
-
+// Build switches (the only UFM_* names the preprocessor tests; something committed builds each of them):
+//   UFM_TILE            tile edge, 16 (default) or 32
+//   UFM_STRICT_FENCES   the checking build of the resident kernel's memory protocol (libufm_strict.so)
+//   UFM_REGION_NG0      tiles in the LDS copy of the block replan kernel's write-back (libufm_strict.so: 2)
+//   UFM_TIMING          in-kernel timing and traces (diagnostic builds of tools/)
+//   UFM_SWEEPSTAT       what the patch sweeps find (diagnostic build of tools/sweep_stats.py)
+// Every other UFM_* name is a tuned constant: a constexpr next to the measurement that chose its value.  Variants that were measured
+// and not kept are in DESIGN.md section 11 and, where they were more than a line, as patches under tools/experiments/.
 #ifndef UFM_TILE
 #define UFM_TILE 16
 #endif
@@ -14,95 +21,32 @@ constexpr int PT = T / 4;      // 4x4-node patches per tile side
 constexpr int PR = PT / 4;     // patches per wave per side (the 16 waves form a 4x4 grid)
 constexpr int PPW = PR * PR;   // patches per wave: 4 (T = 32) or 1 (T = 16)
 constexpr int NTHR = 1024;     // 16 waves; four lanes per node, each wave owns PPW 4x4-node patches
-#ifndef UFM_RELAX_WAVES
-#define UFM_RELAX_WAVES 4      // waves per SIMD the relax kernel is compiled for (4: one 1024-thread workgroup per CU)
-#endif
-#ifndef UFM_CAUSAL_FILTER
-#define UFM_CAUSAL_FILTER 1    // do not wake a neighbour tile that a changed border value cannot influence
-#endif
-#ifndef UFM_STEP_FILTER
-#define UFM_STEP_FILTER 1        // do not wake a neighbour tile whose border is less than one step above this tile's (see k_relax write-back)
-#endif
+constexpr int UFM_RELAX_WAVES = 4;      // waves per SIMD the relax kernel is compiled for (4: one 1024-thread workgroup per CU)
 // MS-DFM (operator ALGO_DFM1 below) converges without cut-offs on almost every map; these are its livelock guard only: block
 // Gauss-Seidel between two tiles can cycle through a finite set of last-bit states (2048^2, seed 1006): after LAX visits of a tile
 // in one step a 1-ulp rise is left alone, after QUIET visits a change of <= 4 ulp no longer wakes the neighbours
-#ifndef UFM_DFM1_LAX_VISITS
-#define UFM_DFM1_LAX_VISITS 64
-#endif
-#ifndef UFM_DFM1_QUIET_VISITS
-#define UFM_DFM1_QUIET_VISITS 96
-#endif
-#ifndef UFM_DPP_MIN_ASM
-#define UFM_DPP_MIN_ASM 1
-#endif
-#ifndef UFM_STATIC_FIRST
-#define UFM_STATIC_FIRST 1     // cursor hand-out: first tile of a workgroup by index, the rest through the cursor
-#endif
-#ifndef UFM_LPT
-#define UFM_LPT 1              // longest-expected-first hand-out of the ready list
-#endif
-#ifndef UFM_LONG_SWEEPS
-#define UFM_LONG_SWEEPS 8      // a visit that took at least this many sweeps per wave counts as long
-#endif
-#ifndef UFM_LDS_FENCE
-#define UFM_LDS_FENCE 1        // 1: workgroup-scope release fence between a sweep's value write and its wake bits
-                               // (0: compiler-only ordering, relying on the LDS executing one wave's DS instructions in
-                               //  issue order -- all tests pass and nothing measurable is gained, so the fence stays)
-#endif
-#if UFM_LDS_FENCE
+constexpr int UFM_DFM1_LAX_VISITS = 64;
+constexpr int UFM_DFM1_QUIET_VISITS = 96;
+constexpr int UFM_LONG_SWEEPS = 8;      // a visit that took at least this many sweeps per wave counts as long (longest-expected-first hand-out of the ready list)
+// workgroup-scope release fence between a sweep's value write and its wake bits (with compiler-only ordering, relying on the LDS executing one
+// wave's DS instructions in issue order, all tests pass and nothing measurable is gained, so the fence stays)
 #define UFM_SWEEP_FENCE() __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup")
-#else
-#define UFM_SWEEP_FENCE() asm volatile("" ::: "memory")
-#endif
-#ifndef UFM_EARLY_HANDOFF
-#define UFM_EARLY_HANDOFF 1    // resident kernel, FD / SG: a border patch that has gone quiet writes its lowered border values out and
-#endif                         // queues the neighbours at once, while the rest of the tile is still being swept (k_relax)
-#ifndef UFM_HINT_SAMPLE
-#define UFM_HINT_SAMPLE 64     // hints (other owners' smallest priorities) a visit loads ahead for the choice of the next tile
-#endif
-#ifndef UFM_LEAN_LOOKS
-#define UFM_LEAN_LOOKS 1       // looks of an idle workgroup: a sample of the hints, other owners' words only where a hint lies inside the band, no lock scan
-#endif
-#ifndef UFM_LOOK_HINTS
-#define UFM_LOOK_HINTS 128     // hints an idle workgroup's look loads (UFM_LEAN_LOOKS; workgroup 0 loads all)
-#endif
-#ifndef UFM_LOOK_SLEEP
-#define UFM_LOOK_SLEEP (UFM_LEAN_LOOKS ? 127 : 32)   // pause of a workgroup that found nothing to visit before it looks again (x 64 clocks; measured r2: 32 / 64 / 127 -> 15.0 / 14.9 / 14.9 ms)
-#endif
-#ifndef UFM_STEAL_VICTIMS
-#ifndef UFM_FOLLOW
-#define UFM_FOLLOW 3             // resident kernel: a workgroup with nothing of its own to go on with takes the neighbour it has just queued with the smallest priority (k_relax); the
-                                 // number of neighbours it tries (the best one is often in a visit already).  FD 4096^2 plan kernel 13.84 (0) / 13.6 (1) / 13.43 (2) / 13.36 (3) / 13.38 ms (8)
-#endif
-#define UFM_STEAL_VICTIMS 4    // owners whose words an idle workgroup looks at per look (k_relax, own_steal)
-#endif
-#ifndef UFM_EARLY_POLLS
-#define UFM_EARLY_POLLS 2      // ... its queue words follow after this many looks of the idle wave at its wake bits (round 4, looks 128 clocks apart: 1 / 2 / 6 / 10 / 16
-                               // looks -> SG 2048^2 plan kernel 5.00 / 5.00 / 5.15 / 5.21 / 5.32 ms; the wave waits for its stores first in any case)
-#endif
+constexpr int UFM_HINT_SAMPLE = 64;     // hints (other owners' smallest priorities) a visit loads ahead for the choice of the next tile
+constexpr int UFM_LOOK_HINTS = 128;     // hints an idle workgroup's look loads (a sample; workgroup 0 loads all)
+constexpr int UFM_LOOK_SLEEP = 127;     // pause of a workgroup that found nothing to visit before it looks again (x 64 clocks; measured r2: 32 / 64 / 127 -> 15.0 / 14.9 / 14.9 ms)
+constexpr int UFM_FOLLOW = 3;           // resident kernel: a workgroup with nothing of its own to go on with takes the neighbour it has just queued with the smallest priority (k_relax); the
+                                        // number of neighbours it tries (the best one is often in a visit already).  FD 4096^2 plan kernel 13.84 (0) / 13.6 (1) / 13.43 (2) / 13.36 (3) / 13.38 ms (8)
+constexpr int UFM_STEAL_VICTIMS = 4;    // owners whose words an idle workgroup looks at per look (k_relax, own_steal)
+constexpr int UFM_EARLY_POLLS = 2;      // early hand-off: a quiet border patch's queue words follow its values after this many looks of the idle wave at its wake bits (round 4, looks 128 clocks apart:
+                                        // 1 / 2 / 6 / 10 / 16 looks -> SG 2048^2 plan kernel 5.00 / 5.00 / 5.15 / 5.21 / 5.32 ms; the wave waits for its stores first in any case)
 // Issue priority (s_setprio): waves that sweep, stage or write back run above waves that only look -- an idle wave of a visit at its wake bits,
 // a workgroup without a tile at the queue words -- so that on a SIMD the looks do not take issue slots from the wave on the chain.  In the 8-wave form
 // (two visits per CU; FD 4096^2 plan kernel 14.0 -> 13.6 ms, MS-DFM 2048^2 11.9 -> 11.7); with 16 waves per visit, whose idle waves also fetch the tile's
 // new inputs during the visit (in-visit refresh), it costs visits: SG 2048^2 51 k -> 55 k, 5.25 -> 5.4 ms -- not there.
-#ifndef UFM_VISIT_PRIO
-#define UFM_VISIT_PRIO 3
-#endif
-#if UFM_VISIT_PRIO
+constexpr int UFM_VISIT_PRIO = 3;
 #define UFM_SETPRIO(x) __builtin_amdgcn_s_setprio(x)
-#else
-#define UFM_SETPRIO(x) do {} while (0)
-#endif
-#ifndef UFM_IDLE_SLEEP
-#define UFM_IDLE_SLEEP 2      // an idle wave of a tile visit looks at its wake bits this often (x 64 clocks).  Round 4, with the issue priorities in place: 1 / 2 / 4 / 8 ->
-#endif                       // FD 4096^2 plan kernel 13.62 / 13.53 / 13.63 / 13.8 ms, SG 2048^2 (16 waves, in-visit refresh) 5.07 / 5.10 / 5.25 / 5.46 ms
-#ifndef UFM_DIRWAKE
-#define UFM_DIRWAKE 0          // resident kernel: a re-visit wakes the patches along the halo entries that changed since the tile's last visit, not all sixteen
-#endif                         // (round 4, measured, diagnostic builds only: FD 4096^2 evaluations per element 29.3 -> 27.4, plan kernel 14.10 -> 14.50 ms; 8192^2 24.3 -> 22.9,
-                               //  35.1 -> 35.7 ms; MS-DFM 2048^2 100 -> 97, 11.35 -> 11.6 ms: the kernel is bound by its chain of dependent visits, not by its work -- DESIGN.md 11)
-#ifndef UFM_DAG
-#define UFM_DAG 0              // round 4 experiment, diagnostic builds only (tools/dag_probe.py, lib build/exp/libufm_dag.so): first visits of the resident
-#endif                         // kernel gated by an arrival estimate (DevParams::dag_*).  Measured: -28 % tile visits, -36 % evaluations, +10 % time.
-constexpr bool DAG = UFM_DAG != 0;
+constexpr int UFM_IDLE_SLEEP = 2;       // an idle wave of a tile visit looks at its wake bits this often (x 64 clocks).  Round 4, with the issue priorities in place: 1 / 2 / 4 / 8 ->
+                                        // FD 4096^2 plan kernel 13.62 / 13.53 / 13.63 / 13.8 ms, SG 2048^2 (16 waves, in-visit refresh) 5.07 / 5.10 / 5.25 / 5.46 ms
 // HBM layout of the field: tile-major.  A tile's T x T values are contiguous
 // (1 KB for T = 16: eight 128-B lines); next to them every tile keeps a *ring*: copies of the border
 // values of its eight neighbours (top row, bottom row, left column, right column, four corners --
@@ -113,36 +57,17 @@ constexpr int TT = T * T;                                        // floats per t
 // Which patches a wave of a 16-wave workgroup owns (the block kernel of ufm_region.h; the 16-wave tile visits of k_relax with 16 x 16 tiles).
 // Patch (pr, pc) belongs to the wave with the index ((pr & 3) << 2) | (pc & 3); hardware wave p of the workgroup
 // runs on SIMD p & 3 (read back from HW_ID: tools/replan_timeline.py prints it).  With index = p the four waves of a patch COLUMN class share one
-// SIMD: a front that runs along the rows keeps one SIMD busy and three idle.  UFM_WAVE_PERM: hardware wave p takes the index whose column
+// SIMD: a front that runs along the rows keeps one SIMD busy and three idle.  wave_index16: hardware wave p takes the index whose column
 // class is p >> 2 and whose row class is ((p & 3) - 2 * (p >> 2)) & 3, i.e. the patch class (r, c) runs on SIMD (r + 2c) & 3 -- neighbours along
 // a row class two SIMDs apart, along a column one, along either diagonal one or three: no direction of a front lands on a single SIMD.
-#ifndef UFM_WAVE_PERM
-#define UFM_WAVE_PERM 1
-#endif
-// ... and of an 8-wave visit (the wave with index w owns the two patches with (pr + 2 pc) mod 8 = w): UFM_WAVE_PERM8
-#ifndef UFM_WAVE_PERM8
-#define UFM_WAVE_PERM8 1
-#endif
+__device__ __forceinline__ int wave_index16(int p) {      // class (r, c) on SIMD (r + 2c) & 3
+    return ((((p & 3) - 2 * (p >> 2)) & 3) << 2) | (p >> 2);
+}
+// ... and of an 8-wave visit (the wave with index w owns the two patches with (pr + 2 pc) mod 8 = w): index w on
+// SIMD ((w >> 1) + 2 (w & 1)) & 3 -- the patches of a row AND of a column on four SIMDs
 __device__ __forceinline__ int wave_index8(int p) {
-#if UFM_WAVE_PERM8 == 1      // index w on SIMD ((w >> 1) + 2 (w & 1)) & 3: the patches of a row AND of a column on four SIMDs
     const int s = p & 3;
     return (p >> 2) ? 2 * ((s + 2) & 3) + 1 : 2 * s;
-#else
-    return p;
-#endif
-}
-__device__ __forceinline__ int wave_index16(int p) {
-#if UFM_WAVE_PERM == 1      // class (r, c) on SIMD (r + 2c) & 3
-    return ((((p & 3) - 2 * (p >> 2)) & 3) << 2) | (p >> 2);
-#elif UFM_WAVE_PERM == 2    // (2r + c) & 3
-    return ((p >> 2) << 2) | (((p & 3) - 2 * (p >> 2)) & 3);
-#elif UFM_WAVE_PERM == 3    // (r + c) & 3
-    return ((((p & 3) - (p >> 2)) & 3) << 2) | (p >> 2);
-#elif UFM_WAVE_PERM == 4    // (r - c) & 3
-    return ((((p & 3) + (p >> 2)) & 3) << 2) | (p >> 2);
-#else
-    return p;
-#endif
 }
 constexpr int RING = (4 * T + 4 + 31) / 32 * 32;                 // floats per ring record (4T+4 used)
 constexpr int RING_TOP = 0, RING_BOT = T, RING_LEFT = 2 * T, RING_RIGHT = 3 * T, RING_CORNER = 4 * T;   // corner order: TL TR BL BR
@@ -222,8 +147,7 @@ struct DevParams {
     uint8_t *bp;                // [NT][T][T] back-pointers (the level-1/2 planners' INFO, FD impl:86-111, SG :131-166, DFM :73-99), same layout as G: which of
                                 // the operator's candidates gives the element's value, and which of its inputs that leans on (bp_byte); BP_NONE: goal / never set
     float *ring;                // [NT][RING] border values of each tile's eight neighbours (+inf where there is none)
-    float *seen;                // [NT][RING] resident kernel: the halo values a tile's last visit converged against (entries as `ring`), [RING - 1] = 1.0f if that
-                                // visit did converge: a later visit of the same step wakes only the patches along halo entries that have changed since (UFM_DIRWAKE)
+    float *seen;                // unused (null): the record of the direction-aware wake-up experiment (tools/experiments/r4_dirwake.diff) -- see dag_a
     uint8_t *cost;              // [nmaps][L][W] the raster (Graph::map_)
     uint8_t *costT;             // [NT][CTS] per tile, the cost bytes its visit needs: cells (x0-1..x0+T-1, y0-1..y0+T-1) of a
                                 // node tile, (x0..x0+T-1, y0..y0+T-1) of a cell tile (DFM), row-major; 255 outside the map
@@ -257,14 +181,15 @@ struct DevParams {
     int *own_lock;              // [OWN_NW][own_slots] 1 while the tile is being visited: whoever takes a tile (its owner, or an idle workgroup helping
                                 // out) needs both the queue word AND this lock -- an activation that lands during a visit re-queues the tile at once
     int *own_min;               // [OWN_NW] smallest priority each owner holds (queued or in flight): a hint for the ordering band, not exact
-    // Round 4 experiment: first visits gated by an approximate arrival order.  dag_a[tile] = estimate of when the front reaches
-    // the tile (any monotone proxy); a tile's FIRST visit waits until every neighbour that the estimate puts clearly before it (dag_a < dag_thr
-    // of the tile) has had its first visit: dag_left counts those neighbours down (grouped like own_prio).  Later visits are not gated.
-    float *dag_a;               // [NT]
-    float *dag_thr;             // [NT]
-    int *dag_left;              // [OWN_NW][own_slots]
-    int dag_on;                 // 0: off (ordering band only)
-    int dag_patience;           // looks without an eligible tile after which a workgroup takes a held one anyway (an estimate may name a neighbour that never comes)
+    // Unused (null / 0), nothing reads or writes them: the fields of the arrival-order gating experiment (tools/experiments/r4_dag_gating.diff).  They -- and
+    // `seen` above -- still hold their 48 bytes because taking them out moves the offsets of the kernel arguments behind them, and k_replan_region, which spills
+    // ~120 SGPRs, then allocates its registers differently (SGPR spills 124 -> 120 ... 122 -> 125, 9946 -> 11077 instruction lines in the FD instantiation).
+    // Removing them is a change of its own, to be made with the replan benchmark in hand.
+    float *dag_a;
+    float *dag_thr;
+    int *dag_left;
+    int dag_on;
+    int dag_patience;
     unsigned long long own_limit;   // wall-clock ticks (100 MHz) after which the resident kernel hands back to the launch chain
     int own_flags;              // diagnostics: 1 = no tile taken ahead (every visit starts with a fresh look at the queue)
     int own_slots, own_sx, own_sy;  // words per owner = nmaps * own_sx * own_sy; blocks of 16 x (1 << own_ys) tiles per map side
@@ -446,9 +371,7 @@ template <bool COH> __device__ __forceinline__ void st_f(float *p, float v) {
 __device__ unsigned long long g_tdiag[64];
 // trace of the lowering launches UFM_TRACE_K0 .. +7: per record {launch | block<<16 | kind<<40, t0, t1, sweeps};
 // kind 0 = tile visit (pop .. end), 1 = block lifetime (entry .. exit)
-#ifndef UFM_TRACE_K0
-#define UFM_TRACE_K0 300
-#endif
+constexpr int UFM_TRACE_K0 = 300;
 __device__ unsigned long long g_trace[4 * 16384];
 __device__ unsigned int g_ntrace;
 // per-wave timeline of ONE tile visit (the first long-list visit of workgroup 0 in launch UFM_TRACE_K0):

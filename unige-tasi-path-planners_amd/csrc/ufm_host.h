@@ -56,10 +56,6 @@ struct Engine {
                                      // 8: early hand-off waits for its stores inside the sweep loop; 16: no in-visit halo refresh; 32: idle workgroups do not help out;
                                      // 64: a workgroup does not follow the front (the neighbour it has just queued); 128: ... follows it beyond the ordering band too
     int owned_waves = 0;             // waves per tile visit of the resident kernel: 16 (256 workgroups), 8 (512), 0 = by the size of the job
-    int dag_mode = 0;                // round 4 experiment: first visits gated by an arrival estimate.  0 off; 1: the estimate handed in through ufm_debug_set_tile_order
-    bool dag_have = false;           // ... an estimate is in P.dag_a
-    float dag_kappa = 0.5f;          // ... a neighbour counts as clearly earlier below own estimate - kappa x (own - earliest neighbour's)
-    int dag_patience = 16;           // ... looks without an eligible tile before a workgroup takes a held one anyway
     bool dfm_follow_info = false;    // MS-DFM level 1: the invalidation follows the stored back-pointer bytes (k_relax / k_replan_region<ALGO_DFM1_INFO>)
     bool use_region = true;          // replans: one workgroup runs both phases in LDS on the block around the patch (ufm_region.h);
                                      // the launch chain only takes over when work is left outside the block
@@ -198,9 +194,9 @@ void Engine::release() {
     drop_graphs();                       // captured kernel arguments hold these pointers
     deferred.clear();
     std::memset(&graph_sig, 0, sizeof(graph_sig));
-    void *ptrs[] = {P.G, P.Gprev, P.bp, P.ring, P.seen, P.cost, P.costT, P.goal, P.cand, P.ready, P.hint, P.rank, P.park, P.pflag, P.pprio,
+    void *ptrs[] = {P.G, P.Gprev, P.bp, P.ring, P.cost, P.costT, P.goal, P.cand, P.ready, P.hint, P.rank, P.park, P.pflag, P.pprio,
                     P.queued, P.prio, P.start, P.bnd, P.dyn, P.spos, P.touched, P.fresh, P.tlist, P.sflag, P.slist, P.slist2,
-                    P.mark, P.num_updated, P.consume, P.lmax, P.own_prio, P.own_lock, P.own_min, P.dag_a, P.dag_thr, P.dag_left, P.ctr, d_scratch};
+                    P.mark, P.num_updated, P.consume, P.lmax, P.own_prio, P.own_lock, P.own_min, P.ctr, d_scratch};
     for (void *q : ptrs) if (q) hipFree(q);
     P = DevParams{};                     // every pointer null again: a failed alloc() can be released, and released twice
     d_scratch = nullptr;
@@ -240,7 +236,6 @@ int Engine::alloc(int width, int length) {
     dmalloc(P.Gprev, gbytes);
     dmalloc(P.bp, P.gstride * nmaps);
     dmalloc(P.ring, (size_t)P.NT * RING * sizeof(float));
-    dmalloc(P.seen, UFM_DIRWAKE ? (size_t)P.NT * RING * sizeof(float) : sizeof(float));
     dmalloc(P.cost, P.cstride * nmaps);
     dmalloc(P.costT, (size_t)P.NT * CTS);
     dmalloc(P.goal, sizeof(int) * 2 * nmaps);
@@ -270,10 +265,6 @@ int Engine::alloc(int width, int length) {
     dmalloc(P.own_prio, sizeof(int) * own_words());
     dmalloc(P.own_lock, sizeof(int) * own_words());
     dmalloc(P.own_min, sizeof(int) * OWN_NW);
-    dag_have = false;
-    dmalloc(P.dag_a, sizeof(float) * (size_t)P.NT);
-    dmalloc(P.dag_thr, sizeof(float) * (size_t)P.NT);
-    dmalloc(P.dag_left, sizeof(int) * own_words());
     dmalloc(P.ctr, sizeof(DevCounters));
     dmalloc(d_scratch, sizeof(int) * (4 * nmaps + 16));
     if (rc != UFM_OK) { release(); return rc; }
@@ -452,7 +443,7 @@ int Engine::launch_relax(int mode, float rbound, hipEvent_t e0, hipEvent_t e1) {
     // a short queue (replans: a handful of tiles per launch) does not need the whole chip: a small
     // grid starts, and when there is nothing left to do ends, sooner
     if (!dyn && last_active <= small_grid / 2 && small_grid < grid_relax) g = dim3(small_grid);
-    if (dyn && UFM_STATIC_FIRST) g = dim3(std::min(grid_relax, dyn_grid));   // one resident workgroup per CU
+    if (dyn) g = dim3(std::min(grid_relax, dyn_grid));   // one resident workgroup per CU
     if (dyn) {
         if (mode == MODE_LOWER) k_triage<MODE_LOWER><<<64, 256, 0, stream>>>(P, iter[q], delta, rbound);
         else k_triage<MODE_RAISE><<<64, 256, 0, stream>>>(P, iter[q], delta, rbound);
@@ -509,9 +500,6 @@ int Engine::owned_phase() {
     //  SG 2048^2 7.08 against 6.55, 1024^2 3.40 against 2.84; MS-DFM, whose visits are longer and which has no early hand-off, 2048^2 13.1 against 15.0)
     const bool half = T == 16 && (owned_waves == 8 || (owned_waves == 0 && (nmaps > 1 || P.NTm > (algo == UFM_ALGO_DFM ? 12000 : 50000))));
     own_layout(half ? 5 : 4);
-    P.dag_on = (DAG && dag_mode != 0 && dag_have) ? 1 : 0;
-    P.dag_patience = dag_patience;
-    if (P.dag_on) k_dag_setup<<<256, 256, 0, stream>>>(P, dag_kappa);
     k_own_import<<<64, 256, 0, stream>>>(P, k);
     // 16 waves per tile visit, one visit per CU -- or 8 and two: a visit is then ~17 % longer and a CU makes 1.7 x as many.  That pays
     // where there are always more tiles to visit than workgroups (several maps, or a front as long as that of an 8192^2 map); a single
@@ -898,7 +886,6 @@ int Engine::step(ufm_stats *out) {
         RegionJobs rjs{};
         bool regioned = false;
         {
-            const bool nodes = algo != UFM_ALGO_DFM;
             // the block of one map: around its consumed rectangles; false if they do not fit into one block
             auto place_job = [&](RegionJob &j, const ReplanBegin &b, int m) {
                 if (!region_fits(b.rect, b.nrect, m, &j.tx0, &j.ntx, &j.ty0, &j.nty)) return false;

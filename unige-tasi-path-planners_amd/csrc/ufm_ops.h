@@ -145,7 +145,6 @@ template <> struct QuadConsts<UFM_ALGO_FD> {
 };
 
 __device__ __forceinline__ float quad_min(float v) {
-#if UFM_DPP_MIN_ASM
     // v_min_f32 with a DPP source operand: one instruction per step instead of mov_dpp + canonicalise + min
     // (IEEE mode: v_min_f32 returns the non-NaN operand like fminf; the values here are never NaN).
     // The s_nop covers the VALU-write -> DPP-read hazard of the second step.
@@ -156,12 +155,6 @@ __device__ __forceinline__ float quad_min(float v) {
                  "v_min_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf"
                  : "=&v"(r) : "v"(v));
     return r;
-#else
-    int x = __float_as_int(v);
-    v = fminf(v, __int_as_float(__builtin_amdgcn_update_dpp(x, x, 0xB1, 0xF, 0xF, false)));   // quad_perm [1,0,3,2]
-    x = __float_as_int(v);
-    return fminf(v, __int_as_float(__builtin_amdgcn_update_dpp(x, x, 0x4E, 0xF, 0xF, false)));   // quad_perm [2,3,0,1]
-#endif
 }
 
 // Back-pointers (DevParams::bp), one byte per element: (code << 2) | dep.  Written once per step, when it has converged, for every tile the step

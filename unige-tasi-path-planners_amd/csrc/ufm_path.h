@@ -431,9 +431,6 @@ __device__ float dfm_stencil(int ca, int cb, float ga, float gb, float tau, floa
 __device__ __forceinline__ int info_from_byte(const PathField &F, int code, float g, int x, int y, int &b0, int &b1) {
     b0 = -1; b1 = -1;
     int key = 0xFF;
-#ifdef UFM_BPDEBUG
-    if (code == 0xFD) { b0 = -3; b1 = -3; return 0xFD; }
-#endif
     if (code != 0xFF && g < INFINITY) {
         const int q = (code >> 3) & 3, w = (code >> 2) & 1;      // the byte: (((q << 1) | w) << 2) | dep
         if (F.cells) {

@@ -18,22 +18,12 @@
 // published to the spinning host; otherwise the host carries on with the ordinary launch chain from the queues.
 // A sweep budget bounds every wave (livelock guard): what is still dirty when it runs out goes to the queues too.
 
-#ifndef UFM_REGION_IDLE_SLEEP_RAISE
-#define UFM_REGION_IDLE_SLEEP_RAISE 8    // ... in the node planners' invalidation phase, whose sweeps are a few loads and a compare
-#endif
 // Waves that sweep run at a higher issue priority than waves that look for work (s_setprio): the looks of the idle waves of a SIMD do not
 // take the issue slots of the one that is on the chain
-#ifndef UFM_REGION_PRIO
-#define UFM_REGION_PRIO 2
-#endif
-#if UFM_REGION_PRIO
+constexpr int UFM_REGION_PRIO = 2;
 #define UFM_REGION_SETPRIO(x) __builtin_amdgcn_s_setprio(x)
-#else
-#define UFM_REGION_SETPRIO(x) do {} while (0)
-#endif
-#ifndef UFM_REGION_IDLE_SLEEP
-#define UFM_REGION_IDLE_SLEEP 8          // an idle wave of the block kernel looks at its wake words this often (x 64 clocks): 1 / 4 / 16 / 32 / 64 -> 100 replans 18.9 / 18.0 / 17.6 / 17.6 / 17.8 ms (the looks of twelve idle waves take issue slots and LDS cycles from the four that sweep)
-#endif
+constexpr int UFM_REGION_IDLE_SLEEP = 8;         // an idle wave of the block kernel looks at its wake words this often (x 64 clocks): 1 / 4 / 16 / 32 / 64 -> 100 replans 18.9 / 18.0 / 17.6 / 17.6 / 17.8 ms (the looks of twelve idle waves take issue slots and LDS cycles from the four that sweep)
+constexpr int UFM_REGION_IDLE_SLEEP_RAISE = 8;   // ... in the node planners' invalidation phase, whose sweeps are a few loads and a compare
 constexpr int RTMAX = 128 / T;            // block edge in tiles (8 for 16 x 16 tiles: field 71 KB + cost bytes 17 KB + back-pointer codes 16 KB of the CU's 160 KB LDS)
 constexpr int RN = RTMAX * T;             // ... in elements (160)
 constexpr int RP = RN + 8;                // LDS pitch of the block's field: rows 4 apart on distinct banks (168 = 5*32 + 8)

@@ -48,10 +48,7 @@ __global__ __launch_bounds__(OWNK == 2 ? NTHR / 2 : NTHR, UFM_RELAX_WAVES) void 
     __shared__ int s_pfh[OWN ? OWN_NW : 1];   // start of the visit in progress (loaded straight into LDS while it sweeps)
     __shared__ int s_se[OWN ? 256 : 1];       // resident kernel: start elements of the first 64 maps (index into G, -1 unused) ...
     __shared__ float s_sh[OWN ? 256 : 1];     // ... and hm * dist(start, element)
-    __shared__ int s_wsel[2];   // resident kernel, UFM_DIRWAKE: [0] the visit ends at the end condition (no sweeps), [1] the tile's last visit converged (its `seen` record is complete)
     __shared__ int s_late;      // resident kernel: thread 0 has seen the time limit pass (no more tiles are taken ahead: the next look leaves)
-    __shared__ int s_held;      // resident kernel, P.dag_on: the last decision saw a queued tile of this workgroup that is still waiting for first visits of its neighbours
-    __shared__ int s_pd[(OWN && DAG) ? NTH : 1];      // ... and the counts of those (dag_left) for this workgroup's first queue words, loaded with s_pf
     __shared__ int s_own[4];    // resident kernel, thread 0's book-keeping: 0 slot whose mark is still to be taken back, 1 slot being visited, 2 visits
     __shared__ unsigned long long s_stat[3];   // thread 4's per-workgroup statistics (visits, sweeps, evaluations), flushed once at the end
     // resident kernel, node planners: border values are handed to the neighbours DURING the visit (early hand-off, below):
@@ -59,7 +56,7 @@ __global__ __launch_bounds__(OWNK == 2 ? NTHR / 2 : NTHR, UFM_RELAX_WAVES) void 
     // smallest border value an early write has changed
     // (16 waves per visit only: with 8 waves and two visits per CU -- the form for jobs that are bound by the number of visits, not by
     //  their chain -- the longer visits cost more than the saved ones bring: 8192^2 plan 41.3 -> 44.0 ms)
-    constexpr bool EARLY = (OWNK == 1 || (OWNK == 2 && UFM_EARLY_HANDOFF > 1)) && UFM_EARLY_HANDOFF && !is_dfm<ALGO>;
+    constexpr bool EARLY = OWNK == 1 && !is_dfm<ALGO>;
     __shared__ float Os[EARLY ? TT : 1];
     __shared__ int s_emin[EARLY ? 16 * 9 : 1];
 #ifdef UFM_TIMING
@@ -130,7 +127,7 @@ __global__ __launch_bounds__(OWNK == 2 ? NTHR / 2 : NTHR, UFM_RELAX_WAVES) void 
     // A workgroup's first tile is the one at its own index -- no round trip to the shared cursor
     // before the first visit (256 same-address atomics across 8 XCDs take microseconds); the launch
     // has one workgroup per CU, so all of them start at once and the longest-first order is kept.
-    bool first_pop = UFM_STATIC_FIRST;
+    bool first_pop = true;
     if (tid == 4) { s_stat[0] = 0ull; s_stat[1] = 0ull; s_stat[2] = 0ull; }   // (thread 4 alone reads and writes them)
     int st_lmax = 0;
     // resident kernel: this workgroup's queue words.  Slots are kept as indices into the whole array of words (owner * own_slots + slot),
@@ -139,10 +136,11 @@ __global__ __launch_bounds__(OWNK == 2 ? NTHR / 2 : NTHR, UFM_RELAX_WAVES) void 
     int *const own_q = OWN ? P.own_prio + (size_t)blockIdx.x * P.own_slots : nullptr;
     const int own_base = OWN ? (int)blockIdx.x * P.own_slots : 0;
     int own_next = -1, own_slot_now = -1;   // (the same in every thread)
-    int prev_gt = -1;                       // the tile of the visit that has just ended (-1: none yet / it ended at the end condition)
+    int prev_gt = -1;                       // the tile of the visit that has just ended (-1: none yet; it is never set back).  With it goes s_bmin as that visit's write-back
+                                            // left it -- all INFBITS after a visit that ended at the end condition: every visit's preface re-initialises s_bmin.  The follow code
+                                            // below reads both BEFORE the first look and must not read s_bmin after one: own_steal uses it as scratch
     int own_hrot = 0;                       // which part of the hints the visit in progress has loaded ahead
-    [[maybe_unused]] int look_rot = 0;      // ... and which part the look of an idle workgroup loads
-    [[maybe_unused]] int held_looks = 0;    // P.dag_on: looks in a row that found only held tiles
+    int look_rot = 0;                       // ... and which part the look of an idle workgroup loads
     const unsigned long long own_t0 = OWN ? wall_clock64() : 0ull;
     if (OWN && tid == 0) { s_own[0] = -1; s_own[1] = -1; s_own[2] = 0; s_late = 0; }
     if constexpr (OWN) {   // the start elements of the first 64 maps: address in G and the heuristic term of their keys (start_bound())
@@ -165,7 +163,7 @@ __global__ __launch_bounds__(OWNK == 2 ? NTHR / 2 : NTHR, UFM_RELAX_WAVES) void 
             // Following the front (round 4, second session; own_flags & 64 turns it off): a workgroup that has nothing of its own to go on with takes the neighbour it has
             // just queued with the smallest priority -- the tile the front moves into -- by the ordinary take, instead of leaving it to its owner's next look
             // (word, look, take: ~10 us of a ring's ~30 even with the chip nearly empty).  Inside the ordering band only (unless own_flags & 128).
-            if (UFM_FOLLOW && !(P.own_flags & 64) && own_next < 0 && prev_gt >= 0) {
+            if (!(P.own_flags & 64) && own_next < 0 && prev_gt >= 0) {
                 if (w == 0) {
                     const int pm = prev_gt / P.NTm, pt = prev_gt - pm * P.NTm, ptx = pt / P.TY, pty = pt - ptx * P.TY;
                     unsigned long long mine = ~0ull;
@@ -208,25 +206,19 @@ __global__ __launch_bounds__(OWNK == 2 ? NTHR / 2 : NTHR, UFM_RELAX_WAVES) void 
             }
             while (own_next < 0) {                             // nothing was taken ahead: look, wait, look again
                 __syncthreads();                               // LDS of the previous visit / round is free
-                // the other owners' hints.  (UFM_LEAN_LOOKS: a sample of them, another one at every look and in an order of this workgroup's own --
+                // the other owners' hints.  (A sample of them, another one at every look and in an order of this workgroup's own --
                 //  the band is a heuristic, as for the visits (UFM_HINT_SAMPLE); workgroup 0, which decides when the phase is over, looks at all.)
                 int hint = INFBITS, ho = tid;
-#if UFM_LEAN_LOOKS
                 const int nh = blockIdx.x == 0 ? P.own_nw : min(P.own_nw, UFM_LOOK_HINTS);
                 ++look_rot;
                 if (blockIdx.x != 0) ho = (int)((unsigned int)(tid + look_rot * nh + (int)blockIdx.x * 61) % (unsigned int)P.own_nw);
                 if (tid < nh && ho != (int)blockIdx.x) hint = __hip_atomic_load(&P.own_min[ho], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
-                if (tid < P.own_nw && tid != (int)blockIdx.x) hint = __hip_atomic_load(&P.own_min[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
                 const int v0 = tid < P.own_slots ? __hip_atomic_load(&own_q[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : INFBITS;
-                const int d0 = (DAG && P.dag_on && tid < P.own_slots) ? __hip_atomic_load(&P.dag_left[own_base + tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
                 const int aborted = tid == 0 ? __hip_atomic_load(&P.ctr->own_abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
-                own_decide(v0, hint, -1, d0, DAG && held_looks >= P.dag_patience);
+                own_decide(v0, hint, -1);
                 const unsigned long long b = s_best;
                 const int votes = s_gmin;
                 const bool have = b != ~0ull;
-                if constexpr (DAG) held_looks = (!have && s_held) ? held_looks + 1 : 0;      // (the same in every thread: s_best / s_held are read behind own_decide's closing barrier)
                 const bool take = have && !(votes & 2);        // inside the ordering band
                 bool stop = false;
                 if (!have && !(votes & 1) && blockIdx.x == 0) {
@@ -316,7 +308,7 @@ __global__ __launch_bounds__(OWNK == 2 ? NTHR / 2 : NTHR, UFM_RELAX_WAVES) void 
         }
         if (DYN && !first_pop) {                           // next ready tile, whoever is free takes it
             __syncthreads();
-            if (tid == 0) s_min = (UFM_STATIC_FIRST ? gridDim.x : 0) + atomicAdd(&P.ctr->rcursor[k & 1], 1);
+            if (tid == 0) s_min = gridDim.x + atomicAdd(&P.ctr->rcursor[k & 1], 1);
             __syncthreads();
             i = s_min;
         }
@@ -382,39 +374,19 @@ __global__ __launch_bounds__(OWNK == 2 ? NTHR / 2 : NTHR, UFM_RELAX_WAVES) void 
         constexpr int CN = CROWS * CROWS;
         const float gl0 = ld_f<OWN>(&Gt[io_on ? tid : 0]);
         const float hv = ld_f<OWN>(&ring[ht >= 0 ? ht : 0]);
-        constexpr bool DIRWAKE = OWN && UFM_DIRWAKE && MODE == MODE_LOWER;
-        float *seen = DIRWAKE ? P.seen + (size_t)gt * RING : nullptr;
-        // (thread ht == -1 loads the record's "complete" flag)
-        const float sv = (DIRWAKE && ht >= -1) ? ld_f<OWN>(&seen[ht >= 0 ? ht : RING - 1]) : 0.0f;
         const int c0 = ct[tid < CN ? tid : 0];
         const int bp0 = BPRAISE ? P.bp[(size_t)gt * TT + (io_on ? tid : 0)] : BP_NONE;
         const int goal_x = P.goal[2 * m], goal_y = P.goal[2 * m + 1];   // (with the rest: read after the barrier they cost two more round trips)
         // resident kernel: the values of the map's start elements, one per lane (for the end condition below)
         const int own_sa = (OWN && focused && tid < 4 && m < 64) ? s_se[m * 4 + tid] : -1;
         const float own_sg = own_sa >= 0 ? ld_f<OWN>(&P.G[own_sa]) : INFINITY;
-        // P.dag_on: the arrival estimate of this tile and the thresholds of its eight neighbours (lane 0..8, 4 = this tile): after its FIRST visit the
-        // tile counts itself off at every neighbour that was waiting for it (the activations' lanes, below)
-        [[maybe_unused]] float dag_mine = 0.0f, dag_nthr = -INFINITY;
-        [[maybe_unused]] int dag_nslot = -1;
-        if constexpr (OWN && DAG) if (P.dag_on && tid < 9 && tid != 4) {
-            const int ntx = tx + tid / 3 - 1, nty = ty + tid % 3 - 1;
-            if (ntx >= 0 && ntx < P.TX && nty >= 0 && nty < P.TY) {
-                const int ngt = m * P.NTm + ntx * P.TY + nty;
-                int o_, s_;
-                own_locate(P, ngt, o_, s_);
-                dag_nslot = o_ * P.own_slots + s_;
-                dag_nthr = P.dag_thr[ngt];
-                dag_mine = P.dag_a[gt];
-            }
-        }
         if (tid == 0) {
             const int seen = atomicAdd(&P.touched[gt], 1);   // visits of this tile in the current step
             const int first = seen == 0;
             if (first) P.tlist[atomicAdd(&P.ctr->tcount, 1)] = gt;
             s_misc[0] = first; s_misc[1] = seen; s_misc[2] = 0; s_misc[3] = 0; s_idle = 0; s_giveup = 0;
         }
-        if (tid < NWV) s_wake[tid] = DIRWAKE ? 0 : (1 << PPWK) - 1;      // (DIRWAKE: set behind the staging barrier, when it is known what there is to wake)
-        if (DIRWAKE && ht == -1) s_wsel[1] = (sv == 1.0f) ? 1 : 0;
+        if (tid < NWV) s_wake[tid] = (1 << PPWK) - 1;
         bool own_parked = false;      // (thread 0)
         if constexpr (OWN) if (focused && w == 0) {
             // End condition: a tile whose priority lies beyond its map's start key (start_bound(): the largest key among the
@@ -434,7 +406,6 @@ __global__ __launch_bounds__(OWNK == 2 ? NTHR / 2 : NTHR, UFM_RELAX_WAVES) void 
                 }
             }
         }
-        if (DIRWAKE && tid == 0) s_wsel[0] = own_parked ? 1 : 0;
         if (tid >= 32 && tid < 41) s_bmin[tid - 32] = INFBITS;
 
         // the tile (contiguous) and its halo: the ring record, in this order (RING_*)
@@ -458,36 +429,6 @@ __global__ __launch_bounds__(OWNK == 2 ? NTHR / 2 : NTHR, UFM_RELAX_WAVES) void 
         }
         if constexpr (EARLY) { if (io_on) Os[tid] = gl0; if (tid < NWV * 9) s_emin[tid] = INFBITS; if (tid == 0) { s_qw[0] = OWN_MARK; s_qw[1] = own_parked ? 0x20000 : 0; } }
         __syncthreads();
-        // the halo entry of thread ht (>= 0) inside the staged tile: row / column -1 or T
-        auto halo_rc = [&](int &hr, int &hc) {
-            if (ht < T) { hr = -1; hc = ht; }
-            else if (ht < 2 * T) { hr = T; hc = ht - T; }
-            else if (ht < 3 * T) { hr = ht - 2 * T; hc = -1; }
-            else if (ht < 4 * T) { hr = ht - 3 * T; hc = T; }
-            else { hr = (ht & 2) ? T : -1; hc = (ht & 1) ? T : -1; }
-        };
-        if constexpr (DIRWAKE) {
-            // What is there to sweep?  The tile's first visit of the step, or one after a visit that ran into the sweep cap: everything.  Otherwise the
-            // tile's own values are a fixed point of the halo its last visit saw (`seen`): only the patches along halo entries that have changed since
-            // can have anything to do -- the others are woken by their neighbours if it comes to that.  (Round 3 woke all sixteen at every visit: half of
-            // the 7.6 M patch sweeps of a 4096^2 plan that found nothing to do.)  A visit that finds no changed entry at all ends after the vote.
-            if (!s_wsel[0]) {
-                if (s_misc[0] || !s_wsel[1]) { if (tid < NWV) s_wake[tid] = (1 << PPWK) - 1; }
-                else if (ht >= 0 && __float_as_int(hv) != __float_as_int(sv)) {
-                    int hr, hc;
-                    halo_rc(hr, hc);
-                    const int r0 = max(hr - 1, 0) / 4, r1 = min(hr + 1, T - 1) / 4, c0_ = max(hc - 1, 0) / 4, c1 = min(hc + 1, T - 1) / 4;
-                    for (int pr_ = r0; pr_ <= r1; ++pr_)
-                        for (int pc_ = c0_; pc_ <= c1; ++pc_) {
-                            int wv, bit;
-                            if constexpr (SKEW) { wv = (pr_ + 2 * pc_) & 7; bit = (pc_ == (wv < 4 ? 0 : (wv >> 1) - 1)) ? 1 : 2; }
-                            else { wv = (pr_ / PR) * 4 + (pc_ / PR); bit = 1 << ((pr_ % PR) * PR + (pc_ % PR)); }
-                            __hip_atomic_fetch_or(&s_wake[wv], bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                        }
-                }
-            }
-            lds_barrier();
-        }
         UFM_TICK(tk1);
 #ifdef UFM_TIMING
         const int dbg_hint = P.hint[gt];
@@ -536,7 +477,7 @@ __global__ __launch_bounds__(OWNK == 2 ? NTHR / 2 : NTHR, UFM_RELAX_WAVES) void 
             // ulp-level rises of replace semantics: a tile whose own border ROSE during a visit
             // therefore comes back once more (s_bmin[4]) and re-reads its neighbours' borders.
             bool need_r = true, need_c = true, need_d = true;
-            if (UFM_CAUSAL_FILTER && MODE == MODE_LOWER) {
+            if (MODE == MODE_LOWER) {
                 const float lo = fminf(gf, gl0);
                 const int cl = max(wb_c - 1, 0) + 1, ch = min(wb_c + 1, T - 1) + 1;     // halo columns / rows that belong
                 const int rl = max(wb_r - 1, 0) + 1, rh = min(wb_r + 1, T - 1) + 1;     // to the edge neighbour itself
@@ -558,7 +499,7 @@ __global__ __launch_bounds__(OWNK == 2 ? NTHR / 2 : NTHR, UFM_RELAX_WAVES) void 
                 // this tile, a step ahead of it -- has nothing to gain and is not woken (41 % of the plan's tile visits
                 // found nothing to do with the test above alone).  Rises keep the test above: an ulp-level correction
                 // must reach whoever was computed from the old value.
-                if (UFM_STEP_FILTER && !is_dfm<ALGO> && gf < gl0) {
+                if (!is_dfm<ALGO> && gf < gl0) {
                     const int crow_r = (er < 0) ? 0 : T;                   // cost row / column of the cells between the tiles
                     const int ccol_c = (ec < 0) ? 0 : T;
                     auto gain_r = [&](int hc) {                           // h = halo row, LDS column hc (node column hc - 1 of the tile)
@@ -581,7 +522,7 @@ __global__ __launch_bounds__(OWNK == 2 ? NTHR / 2 : NTHR, UFM_RELAX_WAVES) void 
                 }
             }
             int need = 0;
-            if (UFM_CAUSAL_FILTER && MODE == MODE_LOWER && (er || ec) && significant && gf > gl0) need |= 8;
+            if (MODE == MODE_LOWER && (er || ec) && significant && gf > gl0) need |= 8;
             if (er && significant && need_r) need |= 1;
             if (ec && significant && need_c) need |= 2;
             if (er && ec && significant && need_d) need |= 4;
@@ -609,7 +550,6 @@ __global__ __launch_bounds__(OWNK == 2 ? NTHR / 2 : NTHR, UFM_RELAX_WAVES) void 
             typedef __attribute__((address_space(3))) void *lds_ptr;
             typedef const __attribute__((address_space(1))) void *glb_ptr;
             __builtin_amdgcn_global_load_lds((glb_ptr)(own_q + min(tid, P.own_slots - 1)), (lds_ptr)(s_pf + (tid & ~63)), 4, 0, 16);              // (16: sc1)
-            if (DAG && P.dag_on) __builtin_amdgcn_global_load_lds((glb_ptr)(P.dag_left + own_base + min(tid, P.own_slots - 1)), (lds_ptr)(s_pd + (tid & ~63)), 4, 0, 16);
             // (the hints: a different quarter or half of them at every visit -- the band is a heuristic, 2 KB of hints per visit next to
             //  1.8 KB of tile data is not)
             ++own_hrot;
@@ -834,7 +774,7 @@ __global__ __launch_bounds__(OWNK == 2 ? NTHR / 2 : NTHR, UFM_RELAX_WAVES) void 
             // exchange is on its way while this visit is written back, and the next visit's loads follow the write-back with no
             // queue round trip in between.  (A fresh look costs two round trips in a row -- words, then exchange -- per visit.)
             own_decide(tid < P.own_slots ? s_pf[tid] : INFBITS, (tid < UFM_HINT_SAMPLE && (tid + own_hrot * UFM_HINT_SAMPLE) % P.own_nw != (int)blockIdx.x) ? s_pfh[tid] : INFBITS,
-                       (own_slot_now >= own_base && own_slot_now < own_base + P.own_slots) ? own_slot_now - own_base : -1, (DAG && P.dag_on && tid < P.own_slots) ? s_pd[tid] : 0, false);
+                       (own_slot_now >= own_base && own_slot_now < own_base + P.own_slots) ? own_slot_now - own_base : -1);
             const unsigned long long b = s_best;
             const bool take = b != ~0ull && !(s_gmin & 2) && !(P.own_flags & 1) && !s_late;
             if (tid == 0) {
@@ -848,17 +788,6 @@ __global__ __launch_bounds__(OWNK == 2 ? NTHR / 2 : NTHR, UFM_RELAX_WAVES) void 
         //  the tests below ahead of the tile loop and carries them through the sweeps -- registers the sweep loop needs)
         int wb_r = io_r, wb_c = io_c;
         asm volatile("" : "+v"(wb_r), "+v"(wb_c));
-        if constexpr (DIRWAKE) if (!s_wsel[0]) {      // the halo this visit has converged against (as staged, plus what an in-visit refresh took in), and whether it did converge
-            if (ht >= 0) {
-                int hr, hc;
-                halo_rc(hr, hc);
-                const float hcur = Gs[(hr + 1) * GP + hc + 1];
-                if (__float_as_int(hcur) != __float_as_int(sv)) st_f<OWN>(&seen[ht], hcur);
-            } else if (ht == -1) {
-                const float f = conv ? 1.0f : 0.0f;
-                if (f != sv) st_f<OWN>(&seen[RING - 1], f);
-            }
-        }
         const float gref = EARLY ? (io_on ? Os[tid] : 0.0f) : gl0;   // what HBM holds (early hand-off: as last written during the visit)
         const float gf = io_on ? Gs[(wb_r + 1) * GP + wb_c + 1] : gref;
         if (gf != gref) {
@@ -905,8 +834,6 @@ __global__ __launch_bounds__(OWNK == 2 ? NTHR / 2 : NTHR, UFM_RELAX_WAVES) void 
                     else activate(P, Q, k + 1, m * P.NTm + ntx * P.TY + nty, s_bmin[tid]);
                 }
             }
-            if constexpr (OWN && DAG) if (tid != 4 && dag_nslot >= 0 && s_misc[0] && dag_mine < dag_nthr)      // first visit done: whoever waited for it has one less to wait for
-                __hip_atomic_fetch_sub(&P.dag_left[dag_nslot], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         if constexpr (OWN) prev_gt = gt;
 #ifdef UFM_TIMING
@@ -976,7 +903,7 @@ __global__ void k_triage(DevParams P, int k, float delta, float rbound) {
         }
         // a launch lasts (work per CU) + (its longest visit) when long visits are handed out last;
         // tiles a front is still crossing (first visit of the step, or many sweeps last time) go first
-        const bool lng = release && UFM_LPT && (P.touched[gt] == 0 || P.hint[gt] >= UFM_LONG_SWEEPS);
+        const bool lng = release && (P.touched[gt] == 0 || P.hint[gt] >= UFM_LONG_SWEEPS);
 #ifdef UFM_TIMING
         if (release && MODE == MODE_LOWER) {
             const float lo = __int_as_float(P.ctr->lmin[Q][r]);

@@ -5,23 +5,16 @@
     // ... something more than an ordering band below my best (which then has to wait).  From this thread's first queue word
     // and one other owner's hint.  Opens and closes with a barrier.  (No reduction tree, no same-address atomics from whole
     // waves -- either costs more than a microsecond here: a handful of lanes have a queued word, and the hints only vote.)
-    // (d0: the tile's count of first visits it still waits for -- P.dag_on --; a tile that is being held is not eligible unless `impatient`)
-    auto own_decide = [&](int v0, int hint, int skip, int d0 = 0, bool impatient = false) {   // skip: the slot of the visit in progress (its turn comes again later)
-        if (tid == 0) { s_best = ~0ull; s_gmin = 0; if constexpr (DAG) s_held = 0; }
+    auto own_decide = [&](int v0, int hint, int skip) {   // skip: the slot of the visit in progress (its turn comes again later)
+        if (tid == 0) { s_best = ~0ull; s_gmin = 0; }
         lds_barrier();
         unsigned long long best = ~0ull;
-        bool held = false;
 #pragma unroll 1
         for (int sl = tid; sl < P.own_slots; sl += NTH) {
             const int v = (sl == tid) ? v0 : __hip_atomic_load(&own_q[sl], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            int dl = 0;
-            if (DAG && P.dag_on && v < INFBITS) dl = (sl == tid) ? d0 : __hip_atomic_load(&P.dag_left[own_base + sl], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const bool ok = !DAG || dl <= 0 || impatient;
-            if (v < INFBITS && sl != skip && ok) best = min(best, ((unsigned long long)(unsigned int)v << 32) | (unsigned int)sl);
-            held = held || (v < INFBITS && sl != skip && !ok);
+            if (v < INFBITS && sl != skip) best = min(best, ((unsigned long long)(unsigned int)v << 32) | (unsigned int)sl);
         }
         if (best != ~0ull) atomicMin(&s_best, best);
-        if constexpr (DAG) if (held) s_held = 1;
         lds_barrier();
         const unsigned long long b = s_best;
         const bool any = hint != INFBITS;
@@ -81,7 +74,6 @@
     // looks at the owner that holds the smallest priority (the hints), at that owner's words, and takes its best queued tile if
     // that lies inside the ordering band -- by the same take the owner uses (own_take_issue), so a tile still has one visitor at a time.
     // All threads call; returns the word taken (its priority in s_own[3]) or -1.
-#if UFM_LEAN_LOOKS
     // (hint: this thread's sample of the hints, ho: the owner it belongs to.  Whose words: owners whose hint lies inside the band above the
     //  smallest hint seen -- up to UFM_STEAL_VICTIMS of them, whichever lanes get there first; every workgroup samples the hints in an order of
     //  its own --, and nobody's when there is no such owner: most looks of an idle workgroup find everything queued beyond the band, and reading
@@ -112,8 +104,7 @@
 #pragma unroll 1
             for (int sl = tid; sl < P.own_slots; sl += NTH) {
                 const int v = __hip_atomic_load(&vq[sl], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const bool held_ = DAG && P.dag_on && v < INFBITS && __hip_atomic_load(&P.dag_left[(size_t)s_bmin[vi] * P.own_slots + sl], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > 0;
-                if (v < INFBITS && !held_) bb = min(bb, ((unsigned long long)(unsigned int)v << 32) | ((unsigned int)vi << 28) | (unsigned int)sl);
+                if (v < INFBITS) bb = min(bb, ((unsigned long long)(unsigned int)v << 32) | ((unsigned int)vi << 28) | (unsigned int)sl);
             }
         }
         for (int o_ = 32; o_; o_ >>= 1) bb = min(bb, (unsigned long long)__shfl_xor((long long)bb, o_));
@@ -147,67 +138,3 @@
         __syncthreads();
         return s_gmin;
     };
-#else
-    int steal_seq = 0;
-    auto own_steal = [&](int hint, int /*ho*/) -> int {
-        unsigned long long hk = hint != INFBITS ? (((unsigned long long)(unsigned int)hint << 32) | (unsigned int)tid) : ~0ull;
-        for (int o_ = 32; o_; o_ >>= 1) hk = min(hk, (unsigned long long)__shfl_xor((long long)hk, o_));
-        if (tid == 0) { s_best = ~0ull; s_gmin = -1; }
-        lds_barrier();
-        if (lane == 0 && hk != ~0ull) atomicMin(&s_best, hk);
-        lds_barrier();
-        const unsigned long long vk = s_best;
-        lds_barrier();
-#ifdef UFM_TIMING
-        if (tid == 0) atomicAdd(&g_sdiag[2], 1ull);
-#endif
-        if (vk == ~0ull) return -1;
-        // (whose words: not the holder of the smallest priority -- its best tile is as a rule the one it is visiting, and every idle
-        //  workgroup would go for the same word -- but a different owner at every look; the smallest hint is the floor of the band)
-        ++steal_seq;
-        unsigned long long bb = ~0ull;         // {priority, which of the owners looked at, slot}
-        int vos[UFM_STEAL_VICTIMS];
-#pragma unroll
-        for (int vi = 0; vi < UFM_STEAL_VICTIMS; ++vi) {
-            const int vo = ((int)blockIdx.x + 1 + (int)((unsigned int)((steal_seq * UFM_STEAL_VICTIMS + vi) * 61 + (int)blockIdx.x * 17) % (unsigned int)(P.own_nw - 1))) % P.own_nw;
-            vos[vi] = vo;
-            const int *vq = P.own_prio + (size_t)vo * P.own_slots;
-#pragma unroll 1
-            for (int sl = tid; sl < P.own_slots; sl += NTH) {
-                const int v = __hip_atomic_load(&vq[sl], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                const int lk = __hip_atomic_load(&P.own_lock[(size_t)vo * P.own_slots + sl], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (v < INFBITS && lk == 0) bb = min(bb, ((unsigned long long)(unsigned int)v << 32) | ((unsigned int)vi << 28) | (unsigned int)sl);
-            }
-        }
-        for (int o_ = 32; o_; o_ >>= 1) bb = min(bb, (unsigned long long)__shfl_xor((long long)bb, o_));
-        if (tid == 0) s_best = ~0ull;
-        lds_barrier();
-        if (lane == 0 && bb != ~0ull) atomicMin(&s_best, bb);
-        lds_barrier();
-        if (tid == 0) {
-            const unsigned long long b2 = s_best;
-#ifdef UFM_TIMING
-            if (b2 != ~0ull) atomicAdd(&g_sdiag[3], 1ull);
-            if (b2 != ~0ull && !(__int_as_float((int)(b2 >> 32)) > __int_as_float((int)(vk >> 32)) + delta)) atomicAdd(&g_sdiag[4], 1ull);
-#endif
-            if (b2 != ~0ull && !(__int_as_float((int)(b2 >> 32)) > __int_as_float((int)(vk >> 32)) + delta)) {
-                int vo = vos[0];
-#pragma unroll
-                for (int vi = 1; vi < UFM_STEAL_VICTIMS; ++vi) if ((int)(((unsigned int)b2 >> 28) & 15u) == vi) vo = vos[vi];
-                const int gw = vo * P.own_slots + (int)((unsigned int)b2 & 0x0FFFFFFFu);
-                int pr = (int)(b2 >> 32);
-                int r_old, r_lk;
-                own_take_issue(gw, pr, r_old, r_lk);
-                if (own_take_resolve(gw, pr, r_old, r_lk)) {
-                    s_own[3] = pr; s_gmin = gw;
-#ifdef UFM_TIMING
-                    atomicAdd(&g_sdiag[5], 1ull);
-#endif
-                    __hip_atomic_fetch_min(&P.own_min[blockIdx.x], pr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // what this workgroup holds now
-                }
-            }
-        }
-        __syncthreads();
-        return s_gmin;
-    };
-#endif
