@@ -234,6 +234,26 @@ typedef struct ufm_path_info {
 } ufm_path_info;
 int ufm_extract_path(ufm_t *p, int max_steps, int lookahead, int allow_indirect,
                      float *path_xy, int cap_points, float *step_costs, int cap_costs, ufm_path_info *info);
+/* Position queries (no reference counterpart: the reference's extractor walks from Graph::start_pos_ only): paths from n_starts
+ * positions of the field AS IT STANDS, in one call -- one wavefront per position, one launch per 65 536 of them -- for a consumer
+ * that asks "what would the path, or the cost to the goal, be from there": several vehicles with one goal, candidate poses, a
+ * lattice of positions.  For every start everything is what ufm_extract_path does from Graph::start_pos_: the same moves, lookahead
+ * and quirks, the same capacity rule (info[k].n_points / n_costs are the full counts, way points and step costs are stored up to
+ * cap_points / cap_costs PER START), n_points == 0: "no valid path exists"; cap_points == 0 && cap_costs == 0 with NULL buffers
+ * returns the totals alone.  The goal is the map's goal.  starts_xy: [n_starts][2]; path_xy: [n_starts][cap_points][2], step_costs:
+ * [n_starts][cap_costs], info: [n_starts], all in the caller's order; e_ms is the wall time of the whole call, in every record.
+ * READ-ONLY on the planner: its start, new_start, queues, field and the statistics of its next step are untouched -- unlike
+ * ufm_set_start + ufm_extract_path, after which the next ufm_step sees a robot that moved.  Needs a map and a goal, not a start.
+ * Patches that are being held (a single planner's small host patches, a batch's "defer_patches") are applied first, as by
+ * ufm_extract_path.
+ * The field is read as it stands: with "focused" = 1 (the default) the values at / beyond the planner's own start key are not final
+ * (never expanded: +inf, or stale) -- the caveat of ufm_read_field and ufm_read_queue; a position there gets the path those values
+ * give.  "focused" = 0 makes every position final.
+ * UFM_ERR_INVALID for the whole call, before anything is launched or written: NULL handle, n_starts < 1, NULL starts_xy or info,
+ * max_steps < 1, a negative capacity or a positive one with a NULL buffer, no map or no goal, a start that is not finite or lies
+ * outside [0, length] x [0, width]. */
+int ufm_extract_paths_from(ufm_t *p, int n_starts, const float *starts_xy, int max_steps, int lookahead, int allow_indirect,
+                           float *path_xy, int cap_points, float *step_costs, int cap_costs, ufm_path_info *info);
 
 /* ---- measurement hooks ---- */
 int ufm_set_profiling(ufm_t *p, int enable);   /* HIP-event timing of every relax launch */
@@ -284,6 +304,13 @@ int ufm_batch_read_changes(ufm_batch_t *b, int i, int cap, int32_t *xy, float *g
 /* all maps in one launch: path_xy [n_maps][cap_points][2], step_costs [n_maps][cap_costs], info [n_maps] */
 int ufm_batch_extract_path(ufm_batch_t *b, int max_steps, int lookahead, int allow_indirect,
                            float *path_xy, int cap_points, float *step_costs, int cap_costs, ufm_path_info *info);
+/* as ufm_extract_paths_from: start k is a position on map map_index[k] (int32 [n_starts], in any order, a map as often as the
+ * caller likes) and walks to that map's goal.  UFM_ERR_INVALID also for a NULL map_index or an index outside the batch; every map
+ * that is named needs a raster and a goal.  A sharded handle groups the starts by the device that owns their map (one launch
+ * sequence per device) and returns them in the caller's order. */
+int ufm_batch_extract_paths_from(ufm_batch_t *b, int n_starts, const int32_t *map_index, const float *starts_xy, int max_steps,
+                                 int lookahead, int allow_indirect, float *path_xy, int cap_points, float *step_costs, int cap_costs,
+                                 ufm_path_info *info);
 
 #ifdef __cplusplus
 }

@@ -25,6 +25,7 @@ SYMBOLS = [
     "ufm_batch_create_sharded", "ufm_batch_shards", "ufm_batch_set_heuristic_multiplier", "ufm_batch_set_map_device",
     "ufm_batch_patch_map_device", "ufm_batch_read_map", "ufm_batch_set_profiling", "ufm_batch_stream", "ufm_read_queue",
     "ufm_track_changes", "ufm_read_changes", "ufm_batch_track_changes", "ufm_batch_read_changes",
+    "ufm_extract_paths_from", "ufm_batch_extract_paths_from",
 ]
 
 
@@ -153,6 +154,8 @@ def load_library():
     L.ufm_read_info_derived.argtypes = [vp, i, i, i, i, vp]
     L.ufm_extract_path.argtypes = [vp, i, i, i, vp, i, vp, i, C.POINTER(PathInfo)]
     L.ufm_batch_extract_path.argtypes = [vp, i, i, i, vp, i, vp, i, C.POINTER(PathInfo)]
+    L.ufm_extract_paths_from.argtypes = [vp, i, vp, i, i, i, vp, i, vp, i, vp]
+    L.ufm_batch_extract_paths_from.argtypes = [vp, i, vp, vp, i, i, i, vp, i, vp, i, vp]
     L.ufm_track_changes.argtypes = [vp, i]
     L.ufm_read_changes.argtypes = [vp, i, vp, vp, vp, vp]
     L.ufm_batch_track_changes.argtypes = [vp, i]
@@ -182,6 +185,20 @@ def _read_changes(call, what, want_info, cap=None):
     _chk(call(cap, xy.ctypes.data, g.ctypes.data, info.ctypes.data if want_info else None, C.addressof(total)), what)
     n = total.value if total.value <= cap else 0
     return xy[:n], g[:n], (info[:n] if want_info else None), total.value
+
+
+def _paths_from(call, what, starts, max_steps):
+    """ufm_extract_paths_from / ufm_batch_extract_paths_from through `call(n, starts, pts, cap_p, costs, cap_c, info)`:
+    ([(points, step_costs, total_cost, total_dist)] in the order of `starts`, the PathInfo array)"""
+    starts = np.ascontiguousarray(starts, np.float32).reshape(-1, 2)
+    n = len(starts)
+    cap_p, cap_c = 3 * max_steps + 1, 2 * max_steps
+    pts = np.zeros((max(n, 1), cap_p, 2), np.float32)
+    costs = np.zeros((max(n, 1), cap_c), np.float32)
+    info = (PathInfo * max(n, 1))()
+    _chk(call(n, starts.ctypes.data, pts.ctypes.data, cap_p, costs.ctypes.data, cap_c, C.addressof(info)), what)
+    return [(pts[k, :info[k].n_points].copy(), costs[k, :info[k].n_costs].copy(),
+             info[k].total_cost, info[k].total_dist) for k in range(n)], info
 
 
 class Planner:
@@ -312,6 +329,15 @@ class Planner:
                                      C.byref(self.path_info)), "ufm_extract_path")
         pi = self.path_info
         return pts[:pi.n_points].copy(), costs[:pi.n_costs].copy(), pi.total_cost, pi.total_dist
+
+    def extract_paths_from(self, starts, max_steps=20, lookahead=True, allow_indirect=True):
+        """position queries (ufm_extract_paths_from): paths from the positions `starts` ([n, 2]) over the field as it stands, in one
+        call, without touching the planner's own start.  Returns a list of (points, step_costs, total_cost, total_dist) in the order
+        of `starts`; the calls' infos are kept in self.path_infos."""
+        out, self.path_infos = _paths_from(
+            lambda n, s, *bufs: self.L.ufm_extract_paths_from(self.h, n, s, int(max_steps), int(lookahead), int(allow_indirect), *bufs),
+            "ufm_extract_paths_from", starts, max_steps)
+        return out
 
     def read_map(self, width, length):
         m = np.empty((length, width), dtype=np.uint8)
@@ -458,6 +484,16 @@ class BatchPlanner:
         self.path_info = info
         return [(pts[k, :info[k].n_points].copy(), costs[k, :info[k].n_costs].copy(),
                  info[k].total_cost, info[k].total_dist) for k in range(n)]
+
+    def extract_paths_from(self, map_index, starts, max_steps=20, lookahead=True, allow_indirect=True):
+        """as Planner.extract_paths_from: start k is a position on map map_index[k] (any order, any number per map)"""
+        mi = np.ascontiguousarray(map_index, np.int32).ravel()
+        assert len(mi) == len(np.asarray(starts).reshape(-1, 2)), "one map index per start"
+        out, self.path_infos = _paths_from(
+            lambda n, s, *bufs: self.L.ufm_batch_extract_paths_from(self.h, n, mi.ctypes.data, s, int(max_steps), int(lookahead),
+                                                                    int(allow_indirect), *bufs),
+            "ufm_batch_extract_paths_from", starts, max_steps)
+        return out
 
     def read_field(self, i):
         nx, ny = self._dims

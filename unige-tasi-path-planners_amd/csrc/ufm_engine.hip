@@ -432,5 +432,16 @@ int ufm_batch_extract_path(ufm_batch_t *b, int max_steps, int lookahead, int all
     }
     return UFM_OK;
 }
+int ufm_extract_paths_from(ufm_t *p, int n_starts, const float *starts_xy, int max_steps, int lookahead, int allow_indirect,
+                           float *path_xy, int cap_points, float *step_costs, int cap_costs, ufm_path_info *info) {
+    return p ? paths_from(&p->e, 1, 1, n_starts, nullptr, starts_xy, max_steps, lookahead, allow_indirect, path_xy, cap_points, step_costs, cap_costs, info)
+             : UFM_ERR_INVALID;
+}
+int ufm_batch_extract_paths_from(ufm_batch_t *b, int n_starts, const int32_t *map_index, const float *starts_xy, int max_steps, int lookahead,
+                                 int allow_indirect, float *path_xy, int cap_points, float *step_costs, int cap_costs, ufm_path_info *info) {
+    if (!b || b->shards.empty() || !map_index) return UFM_ERR_INVALID;
+    return paths_from(b->shards.data(), b->per, b->n_maps, n_starts, map_index, starts_xy, max_steps, lookahead, allow_indirect,
+                      path_xy, cap_points, step_costs, cap_costs, info);
+}
 
 }  // extern "C"

@@ -95,8 +95,9 @@ struct Engine {
     size_t d_info_cap = 0;           // (int32 entries)
     uint8_t *d_pmask = nullptr;      // changed-cell mask of the patch being applied
     size_t d_pmask_cap = 0;
-    PathJob *d_jobs = nullptr, *h_jobs = nullptr;     // path extraction: per-map start / goal (h_: pinned)
-    float *d_path = nullptr, *h_path = nullptr;       // per-map output records
+    PathJob *d_jobs = nullptr, *h_jobs = nullptr;     // path extraction: the walks of one launch (h_: pinned)
+    size_t jobs_cap = 0;                              // jobs per buffer
+    float *d_path = nullptr, *h_path = nullptr;       // per-job output records
     size_t path_cap = 0;                              // floats per buffer
     std::vector<MapState> maps;
     std::vector<PatchRect> pending;
@@ -1412,58 +1413,120 @@ int engine_read_field(Engine *e, int m, int x0, int y0, int nx, int ny, float *g
     return UFM_OK;
 }
 
-// Path extraction for all maps of the engine in one launch (one wavefront per map).
-// path_xy: [nmaps][cap_pts][2], step_costs: [nmaps][cap_costs], info: [nmaps].
-int engine_extract_path(Engine *e, int max_steps, int lookahead, int allow_indirect,
-                        float *path_xy, int cap_pts, float *step_costs, int cap_costs, ufm_path_info *info) {
-    if (!e || !e->allocated || !info || max_steps < 1 || cap_pts < 0 || cap_costs < 0) return UFM_ERR_INVALID;
-    if ((cap_pts > 0 && !path_xy) || (cap_costs > 0 && !step_costs)) return UFM_ERR_INVALID;
-    for (const MapState &ms : e->maps) if (!ms.have_map || !ms.start_set || !ms.goal_set) return UFM_ERR_INVALID;
+// Path extraction: n walks over this engine's maps, one wavefront each (k_extract_path).  Walk k starts at (q[k].sx, q[k].sy) on map
+// q[k].m, ends at that map's goal and is delivered as record q[k].slot of the caller's arrays -- path_xy: [..][cap_pts][2],
+// step_costs: [..][cap_costs], info: [..] (e_ms is the caller's to fill).  The caller has checked the arguments; patches that are being
+// held are applied first (the walk reads the raster).  Launches of at most PATH_CHUNK_JOBS walks, and of at most PATH_CHUNK_FLOATS of
+// output, so that the device and the pinned buffer stay bounded whatever n and max_steps are.
+struct PathQuery { int m; float sx, sy; size_t slot; };
+constexpr size_t PATH_CHUNK_JOBS = 65536, PATH_CHUNK_FLOATS = (size_t)16 << 20;
+
+int engine_walk(Engine *e, const PathQuery *q, size_t n, int max_steps, int lookahead, int allow_indirect,
+                float *path_xy, int cap_pts, float *step_costs, int cap_costs, ufm_path_info *info) {
     HIPCHK(hipSetDevice(e->device));
-    { int rc = e->flush_deferred(); if (rc != UFM_OK) return rc; }   // (the walk reads the raster)
-    const auto t0 = std::chrono::steady_clock::now();
-    const int n = e->nmaps;
+    { int rc = e->flush_deferred(); if (rc != UFM_OK) return rc; }
     // the device keeps what the caller has room for, at most what max_steps moves can produce
     const int dev_pts = std::min(cap_pts, 3 * max_steps + 1), dev_cst = std::min(cap_costs, 2 * max_steps);
     const size_t ostride = PATH_HDR + 2 * (size_t)dev_pts + dev_cst;
-    if (ostride * n > e->path_cap) {
+    const size_t chunk = std::min(n, std::min(PATH_CHUNK_JOBS, std::max<size_t>(PATH_CHUNK_FLOATS / ostride, 1)));
+    if (ostride * chunk > e->path_cap) {
         HIPCHK(hipStreamSynchronize(e->stream));
         if (e->d_path) hipFree(e->d_path);
         if (e->h_path) hipHostFree(e->h_path);
         e->d_path = nullptr; e->h_path = nullptr; e->path_cap = 0;
-        HIPCHK(hipMalloc(&e->d_path, ostride * n * sizeof(float)));
-        HIPCHK(hipHostMalloc(&e->h_path, ostride * n * sizeof(float)));
-        e->path_cap = ostride * n;
+        HIPCHK(hipMalloc(&e->d_path, ostride * chunk * sizeof(float)));
+        HIPCHK(hipHostMalloc(&e->h_path, ostride * chunk * sizeof(float)));
+        e->path_cap = ostride * chunk;
     }
-    if (!e->d_jobs) {
-        HIPCHK(hipMalloc(&e->d_jobs, sizeof(PathJob) * n));
-        HIPCHK(hipHostMalloc(&e->h_jobs, sizeof(PathJob) * n));
+    if (chunk > e->jobs_cap) {
+        HIPCHK(hipStreamSynchronize(e->stream));
+        if (e->d_jobs) hipFree(e->d_jobs);
+        if (e->h_jobs) hipHostFree(e->h_jobs);
+        e->d_jobs = nullptr; e->h_jobs = nullptr; e->jobs_cap = 0;
+        HIPCHK(hipMalloc(&e->d_jobs, sizeof(PathJob) * chunk));
+        HIPCHK(hipHostMalloc(&e->h_jobs, sizeof(PathJob) * chunk));
+        e->jobs_cap = chunk;
     }
-    for (int m = 0; m < n; ++m) e->h_jobs[m] = PathJob{e->maps[m].start_x, e->maps[m].start_y, e->maps[m].goal_x, e->maps[m].goal_y};
-    HIPCHK(hipMemcpyAsync(e->d_jobs, e->h_jobs, sizeof(PathJob) * n, hipMemcpyHostToDevice, e->stream));
     PathField F{};
     F.G = e->P.G; F.cost = e->P.cost;
     F.EX = e->P.EX; F.EY = e->P.EY; F.L = e->P.L; F.W = e->P.W; F.TY = e->P.TY; F.thr = e->thr_uchar;
     F.cells = (e->algo == UFM_ALGO_DFM); F.indirect = allow_indirect != 0;
-    k_extract_path<<<n, 64, 0, e->stream>>>(F, e->P.gstride, e->P.cstride, e->d_jobs, e->d_path, ostride,
-                                            dev_pts, dev_cst, lookahead != 0, max_steps);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(e->h_path, e->d_path, ostride * n * sizeof(float), hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    for (int m = 0; m < n; ++m) {
-        const float *o = e->h_path + ostride * m;
-        ufm_path_info &pi = info[m];
-        std::memcpy(&pi.n_points, &o[0], 4);
-        std::memcpy(&pi.n_costs, &o[1], 4);
-        pi.total_cost = o[2];
-        pi.total_dist = o[3];
-        std::memcpy(&pi.steps, &o[4], 4);
-        const int np = std::min(pi.n_points, dev_pts), nc = std::min(pi.n_costs, dev_cst);
-        if (np > 0) std::memcpy(path_xy + (size_t)m * cap_pts * 2, o + PATH_HDR, sizeof(float) * 2 * np);
-        if (nc > 0) std::memcpy(step_costs + (size_t)m * cap_costs, o + PATH_HDR + 2 * (size_t)dev_pts, sizeof(float) * nc);
+    for (size_t first = 0; first < n; first += chunk) {
+        const size_t cnt = std::min(chunk, n - first);
+        for (size_t k = 0; k < cnt; ++k) {      // (the pinned buffers are free again: every chunk ends with a wait for the stream)
+            const PathQuery &w = q[first + k];
+            e->h_jobs[k] = PathJob{w.sx, w.sy, e->maps[w.m].goal_x, e->maps[w.m].goal_y, w.m};
+        }
+        HIPCHK(hipMemcpyAsync(e->d_jobs, e->h_jobs, sizeof(PathJob) * cnt, hipMemcpyHostToDevice, e->stream));
+        k_extract_path<<<(unsigned)cnt, 64, 0, e->stream>>>(F, e->P.gstride, e->P.cstride, e->d_jobs, e->d_path, ostride,
+                                                            dev_pts, dev_cst, lookahead != 0, max_steps);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(e->h_path, e->d_path, ostride * cnt * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));
+        for (size_t k = 0; k < cnt; ++k) {
+            const float *o = e->h_path + ostride * k;
+            const size_t slot = q[first + k].slot;
+            ufm_path_info &pi = info[slot];
+            std::memcpy(&pi.n_points, &o[0], 4);
+            std::memcpy(&pi.n_costs, &o[1], 4);
+            pi.total_cost = o[2];
+            pi.total_dist = o[3];
+            std::memcpy(&pi.steps, &o[4], 4);
+            const int np = std::min(pi.n_points, dev_pts), nc = std::min(pi.n_costs, dev_cst);
+            if (np > 0) std::memcpy(path_xy + slot * cap_pts * 2, o + PATH_HDR, sizeof(float) * 2 * np);
+            if (nc > 0) std::memcpy(step_costs + slot * cap_costs, o + PATH_HDR + 2 * (size_t)dev_pts, sizeof(float) * nc);
+        }
+    }
+    return UFM_OK;
+}
+
+// what every extraction asks of its buffers
+static bool path_buffers_ok(int max_steps, const float *path_xy, int cap_pts, const float *step_costs, int cap_costs, const ufm_path_info *info) {
+    return info && max_steps >= 1 && cap_pts >= 0 && cap_costs >= 0 && !(cap_pts > 0 && !path_xy) && !(cap_costs > 0 && !step_costs);
+}
+
+// Every map of the engine from its own start (Graph::start_pos_): the walks "one per map, in map order".
+// path_xy: [nmaps][cap_pts][2], step_costs: [nmaps][cap_costs], info: [nmaps].
+int engine_extract_path(Engine *e, int max_steps, int lookahead, int allow_indirect,
+                        float *path_xy, int cap_pts, float *step_costs, int cap_costs, ufm_path_info *info) {
+    if (!e || !e->allocated || !path_buffers_ok(max_steps, path_xy, cap_pts, step_costs, cap_costs, info)) return UFM_ERR_INVALID;
+    for (const MapState &ms : e->maps) if (!ms.have_map || !ms.start_set || !ms.goal_set) return UFM_ERR_INVALID;
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<PathQuery> q((size_t)e->nmaps);
+    for (int m = 0; m < e->nmaps; ++m) q[m] = PathQuery{m, e->maps[m].start_x, e->maps[m].start_y, (size_t)m};
+    { int rc = engine_walk(e, q.data(), q.size(), max_steps, lookahead, allow_indirect, path_xy, cap_pts, step_costs, cap_costs, info); if (rc != UFM_OK) return rc; }
+    const float ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    for (int m = 0; m < e->nmaps; ++m) info[m].e_ms = ms;
+    return UFM_OK;
+}
+
+// Walks from the caller's positions, on the fields as they stand (ufm_extract_paths_from / ufm_batch_extract_paths_from): walk k
+// starts at starts_xy[k] on map map_index[k] (nullptr: map 0) of the handle, whose map i lives in shards[i / per].  Everything is
+// checked before anything is launched or written; nothing of a planner's state is touched (start, new_start, queues: a query, not a
+// set_start).  One launch sequence per shard, results in the caller's order.
+int paths_from(Engine *const *shards, int per, int n_maps, int n_starts, const int32_t *map_index, const float *starts_xy,
+               int max_steps, int lookahead, int allow_indirect, float *path_xy, int cap_pts, float *step_costs, int cap_costs, ufm_path_info *info) {
+    if (n_starts < 1 || !starts_xy || !path_buffers_ok(max_steps, path_xy, cap_pts, step_costs, cap_costs, info)) return UFM_ERR_INVALID;
+    const auto t0 = std::chrono::steady_clock::now();
+    const int n_shards = (n_maps + per - 1) / per;
+    std::vector<std::vector<PathQuery>> q((size_t)n_shards);
+    for (int k = 0; k < n_starts; ++k) {
+        const int i = map_index ? map_index[k] : 0;
+        if (i < 0 || i >= n_maps) return UFM_ERR_INVALID;
+        const Engine *e = shards[i / per];
+        const int m = i % per;
+        if (!e->allocated || !e->maps[m].have_map || !e->maps[m].goal_set) return UFM_ERR_INVALID;
+        const float x = starts_xy[2 * (size_t)k], y = starts_xy[2 * (size_t)k + 1];
+        if (!(x >= 0.0f && x <= (float)e->L && y >= 0.0f && y <= (float)e->W)) return UFM_ERR_INVALID;     // (a NaN fails every comparison)
+        q[i / per].push_back(PathQuery{m, x, y, (size_t)k});
+    }
+    for (int s = 0; s < n_shards; ++s) {
+        if (q[s].empty()) continue;
+        const int rc = engine_walk(shards[s], q[s].data(), q[s].size(), max_steps, lookahead, allow_indirect, path_xy, cap_pts, step_costs, cap_costs, info);
+        if (rc != UFM_OK) return rc;
     }
     const float ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    for (int m = 0; m < n; ++m) info[m].e_ms = ms;
+    for (int k = 0; k < n_starts; ++k) info[k].e_ms = ms;
     return UFM_OK;
 }
 

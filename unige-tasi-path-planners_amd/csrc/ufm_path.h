@@ -8,8 +8,8 @@
 // That is an 8 x 8 fan-out of independent evaluations, each a handful of dependent field / raster
 // reads -- exactly one 64-lane wavefront: lane = 8 * e + l evaluates primary edge e and, when
 // needed, lookahead edge l of e's end point; two 8-lane reductions and one 8-group reduction pick
-// the step.  One wavefront per map, so a batch of maps is extracted in a single launch and the
-// field never leaves HBM.  All arithmetic is the reference's, in fp32 with correctly rounded
+// the step.  One wavefront per walk (PathJob), so a batch of maps, or many start positions on one
+// map, are extracted in a single launch and the field never leaves HBM.  All arithmetic is the reference's, in fp32 with correctly rounded
 // sqrt / divide and hypotf evaluated in fp64 as glibc does, so decisions (argmin, lookahead
 // rejections) fall the same way as on the CPU.
 #pragma once
@@ -274,24 +274,29 @@ __device__ void move_across(const PathField &F, float px, float py, bool vertex,
     }
 }
 
-// Output record per map (floats): [0] points (int bits) [1] step costs (int bits) [2] total_cost
+// Output record per job (floats): [0] points (int bits) [1] step costs (int bits) [2] total_cost
 // [3] total_dist [4] steps taken (int bits) [5..7] reserved, then cap_pts (x,y) pairs, then
 // cap_costs step costs.  Counts beyond the capacities are counted, not stored.
 constexpr int PATH_HDR = 8;
 
+// One walk: from (sx, sy) over the field and the raster of map `map` to that map's goal.  The record of
+// job j is the j-th of `out`: which walk of which caller that is, is the host's business (engine_walk).
 struct PathJob {
-    float sx, sy, gx, gy;     // Graph::start_pos_, goal_pos_
+    float sx, sy, gx, gy;     // Graph::start_pos_ or a caller's position; goal_pos_
+    int map;
 };
 
+// One wavefront per job, one job per workgroup: the walks share nothing (no LDS, no cross-wave state), so
+// any number of them -- every map of a batch from its own start, many starts on one map -- is one launch.
 __global__ __launch_bounds__(64) void k_extract_path(PathField F0, size_t gstride, size_t cstride, const PathJob *jobs,
                                                      float *out, size_t ostride, int cap_pts, int cap_costs,
                                                      int lookahead, int max_steps) {
-    const int m = blockIdx.x, lane = threadIdx.x, e = lane >> 3, l = lane & 7;
+    const int lane = threadIdx.x, e = lane >> 3, l = lane & 7;
+    const PathJob job = jobs[blockIdx.x];
     PathField F = F0;
-    F.G += (size_t)m * gstride;
-    F.cost += (size_t)m * cstride;
-    const PathJob job = jobs[m];
-    float *o = out + (size_t)m * ostride;
+    F.G += (size_t)job.map * gstride;
+    F.cost += (size_t)job.map * cstride;
+    float *o = out + (size_t)blockIdx.x * ostride;
     float *opts = o + PATH_HDR, *ocst = opts + 2 * (size_t)cap_pts;
 
     float lx = job.sx, ly = job.sy;               // `last`

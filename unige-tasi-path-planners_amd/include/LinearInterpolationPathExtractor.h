@@ -46,6 +46,37 @@ class LinearInterpolationPathExtractor {
     cost_.assign(sc.begin(), sc.begin() + info.n_costs);
   }
 
+  // Not in the reference: paths from many positions of the field as it stands, in one call of ufm_extract_paths_from (one
+  // wavefront per position).  A query: the planner's start and this object's path_ / cost_ / totals stay as they are.  One
+  // record per position, in their order, each what extract_path() would leave had the planner started there (an empty path_:
+  // no valid path exists); empty, with last_error set, when the call fails.
+  struct PathFrom {
+    std::vector<Position> path_;
+    std::vector<float> cost_;
+    float total_cost = 0;
+    float total_dist = 0;
+  };
+  std::vector<PathFrom> extract_paths_from(const std::vector<Position> &starts) {
+    std::vector<PathFrom> out;
+    const size_t n = starts.size(), cap_p = 3 * static_cast<size_t>(max_steps) + 1, cap_c = 2 * static_cast<size_t>(max_steps);
+    std::vector<float> from(2 * n), xy(2 * cap_p * n), sc(cap_c * n);
+    for (size_t k = 0; k < n; ++k) { from[2 * k] = starts[k].x; from[2 * k + 1] = starts[k].y; }
+    std::vector<ufm_path_info> info(n);
+    last_error = ufm_extract_paths_from(map.native_handle(), static_cast<int>(n), from.data(), max_steps, lookahead ? 1 : 0,
+                                        allow_indirect_traversals ? 1 : 0, xy.data(), static_cast<int>(cap_p), sc.data(),
+                                        static_cast<int>(cap_c), info.data());
+    if (last_error != UFM_OK) return out;
+    out.resize(n);
+    for (size_t k = 0; k < n; ++k) {
+      out[k].total_cost = info[k].total_cost;
+      out[k].total_dist = info[k].total_dist;
+      const float *p = xy.data() + 2 * cap_p * k;
+      for (int i = 0; i < info[k].n_points; ++i) out[k].path_.emplace_back(p[2 * i], p[2 * i + 1]);
+      out[k].cost_.assign(sc.begin() + cap_c * k, sc.begin() + cap_c * k + info[k].n_costs);
+    }
+    return out;
+  }
+
   std::vector<Position> path_{};
   std::vector<float> cost_{};
   float total_cost = 0;
