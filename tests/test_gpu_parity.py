@@ -466,7 +466,9 @@ def test_replan_submission_variants_agree(algo, lvl):
     (focused mode, below the start key: against the oracle; full field: bitwise between variants in
     full-field mode), num_nodes_updated and num_nodes_expanded must not depend on them.  Includes a
     step with 6 pending patches (more than the fused kernel takes) and one with a 70x70 patch
-    (larger than the single-workgroup patch kernel takes)."""
+    (larger than the single-workgroup patch kernel takes).  The statistics of every step pin the route it took: the resident kernel plans,
+    the default variant replans in the block kernel except on those two steps, a variant without the block kernel never does, and
+    graphs are instantiated exactly where the fused chain may be replayed as one."""
     width = length = 208
     seed = 31
     cost = ufm_amd.synth.cost_map(seed, width, length)
@@ -487,6 +489,7 @@ def test_replan_submission_variants_agree(algo, lvl):
                 p.set_param(name, val)
             p.set_occupancy_threshold(1); p.set_map(cost); p.set_start(*start); p.set_goal(*goal)
             assert p.step() == 0
+            assert p.stats.resident_launches == (0 if v.get("owned") == 0 else 1), v
             log = []
             for k, s, top, left, patch in script:
                 if k == 5:        # six rectangles before one step
@@ -498,6 +501,13 @@ def test_replan_submission_variants_agree(algo, lvl):
                 p.set_start(*s)
                 assert p.step() == 0
                 log.append((p.num_nodes_updated, p.num_nodes_expanded if (full and algo != "DFM") else 0))
+                if not v:                     # default: a single small patch goes through the block kernel, six or a 70 x 70 one cannot
+                    assert p.stats.region_launches == (0 if k in (5, 8) else 1), k
+                elif v.get("region") == 0:
+                    assert p.stats.region_launches == 0, (v, k)
+            if v.get("region") == 0:          # only a fused chain is captured: graph on, and spin_wait on (without it nothing is fused)
+                graphed = v.get("graph", 1) != 0 and v.get("spin_wait", 1) != 0
+                assert (p.stats.graphs_instantiated > 0) == graphed and (graphed or p.stats.graphs_instantiated == 0), v
             results.append((p.g(), log, p.read_map(width, length)))
             p.close()
         for g, log, m in results[1:]:

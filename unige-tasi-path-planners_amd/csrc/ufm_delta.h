@@ -134,10 +134,7 @@ int engine_read_changes(Engine *e, int m, int cap, int32_t *xy, float *g, int32_
     HIPCHK(hipSetDevice(e->device));
     { int rc = e->flush_deferred(); if (rc != UFM_OK) return rc; }   // (MS-DFM's Info pairs read the raster)
     const bool has_info = e->opt_lvl >= 1;
-    PathField F{};
-    F.G = e->P.G + (size_t)m * e->P.gstride; F.cost = e->P.cost + (size_t)m * e->P.cstride;
-    F.EX = e->P.EX; F.EY = e->P.EY; F.L = e->P.L; F.W = e->P.W; F.TY = e->P.TY; F.thr = e->thr_uchar;
-    F.cells = (e->algo == UFM_ALGO_DFM); F.indirect = (e->algo == UFM_ALGO_FD);
+    const PathField F = path_field(e, m);
     const uint8_t *bp = e->P.bp + (size_t)m * e->P.gstride;
     float *base_g = e->trk_g + (size_t)m * e->P.gstride;
     uint8_t *base_key = has_info ? e->trk_key + (size_t)m * e->P.gstride : nullptr;

@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
+#include <algorithm>
 #include <chrono>
 #include <climits>
 #include <cmath>
@@ -195,9 +196,7 @@ static int engine_check_info(Engine *e, uint64_t out[6]) {
     { int rc = e->flush_deferred(); if (rc != UFM_OK) return rc; }
     unsigned long long *d_acc = reinterpret_cast<unsigned long long *>(e->d_scratch);
     HIPCHK(hipMemsetAsync(d_acc, 0, 6 * sizeof(unsigned long long), e->stream));
-    if (e->algo == UFM_ALGO_SG) k_check_bp<UFM_ALGO_SG><<<1024, 256, 0, e->stream>>>(e->P, d_acc);
-    else if (e->algo == UFM_ALGO_DFM) k_check_bp<ALGO_DFM1><<<1024, 256, 0, e->stream>>>(e->P, d_acc);
-    else k_check_bp<UFM_ALGO_FD><<<1024, 256, 0, e->stream>>>(e->P, d_acc);
+    with_lower_op(e->algo, [&](auto a) { k_check_bp<a()><<<1024, 256, 0, e->stream>>>(e->P, d_acc); });
     unsigned long long h[6] = {0, 0, 0, 0, 0, 0};
     HIPCHK(hipMemcpyAsync(h, d_acc, sizeof(h), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));

@@ -9,21 +9,52 @@
         if (_e != hipSuccess) return UFM_ERR_HIP_BASE - (int)_e;          \
     } while (0)
 
-struct PatchRect { int m, x, y, w, h; };
-
+#include "ufm_route.h"
 #include "ufm_path.h"
 
-struct MapState {
-    bool initialize_search = true;   // ReplannerBase.h:149
-    bool goal_set = false;           // :150
-    bool new_goal = false;           // :151
-    bool new_start = false;          // :152
-    bool have_map = false;           // !initialize_graph :148
-    bool start_set = false;
-    float start_x = 0, start_y = 0, goal_x = 0, goal_y = 0;
-    int goal_ex = 0, goal_ey = 0;    // Node()/Cell() of the goal
-    bool goal_elem_valid = false;
-};
+static_assert(RJOBS <= ROUTE_MAX_JOBS && RTMAX >= 3, "ufm_route.h places at most ROUTE_MAX_JOBS blocks");
+constexpr RouteConfig ROUTE_CONFIG{T, RTMAX, RJOBS, ROUTE_MAX_RECTS, 65 * 65};
+
+// ---- which kernel forms exist ----------------------------------------------------
+// The operator id as a compile-time constant, handed to a generic lambda.  Two selectors, because the instantiated forms differ: lowering,
+// finalisation and the checks know FD, SG and MS-DFM; invalidation (k_relax<., MODE_RAISE, .>, k_replan_region) also MS-DFM along the stored bytes.
+template <int V> using IntC = std::integral_constant<int, V>;
+template <class F> void with_lower_op(int algo, F &&f) {
+    if (algo == UFM_ALGO_FD) f(IntC<UFM_ALGO_FD>{});
+    else if (algo == UFM_ALGO_SG) f(IntC<UFM_ALGO_SG>{});
+    else f(IntC<ALGO_DFM1>{});
+}
+template <class F> void with_raise_op(int algo, bool follow_info, F &&f) {
+    if (algo == UFM_ALGO_DFM && follow_info) f(IntC<ALGO_DFM1_INFO>{});
+    else with_lower_op(algo, f);
+}
+template <class F> void with_elements(int algo, F &&f) {     // the patch kernels' <NODES>: FD / SG plan on nodes, MS-DFM on cells
+    if (algo == UFM_ALGO_DFM) f(std::false_type{}); else f(std::true_type{});
+}
+// one launch; with both events given they are attached to the dispatch itself (start / stop time stamps of the kernel, what rocprofv3
+// reports too), not recorded around it as separate packets
+template <class... KA, class... A>
+void launch(void (*k)(KA...), dim3 g, dim3 b, hipStream_t s, hipEvent_t e0, hipEvent_t e1, const A &...a) {
+    if (e0 && e1) hipExtLaunchKernelGGL(k, g, b, 0, s, e0, e1, 0, static_cast<KA>(a)...);
+    else k<<<g, b, 0, s>>>(static_cast<KA>(a)...);
+}
+
+// A grow-on-demand device buffer of capacity `cap`, with a pinned twin if `pinned` is given: wait for the stream if there is something to
+// free (always_sync: in any case), free, allocate `bytes` anew; the capacity is 0 until that has succeeded, `new_cap` then.
+template <class P> int regrow(hipStream_t s, size_t bytes, size_t &cap, size_t new_cap, P *&dev, P **pinned = nullptr, bool always_sync = false) {
+    cap = 0;
+    if (always_sync || dev || (pinned && *pinned)) HIPCHK(hipStreamSynchronize(s));
+    if (dev) hipFree(dev);
+    if (pinned && *pinned) hipHostFree(*pinned);
+    dev = nullptr;                       // nothing dangling if an allocation below fails
+    if (pinned) *pinned = nullptr;
+    HIPCHK(hipMalloc(&dev, bytes));
+    if (pinned) HIPCHK(hipHostMalloc(pinned, bytes));
+    cap = new_cap;
+    return UFM_OK;
+}
+
+template <class... Q> void free_all(hipError_t (*release)(void *), Q *...q) { ((q ? (void)release(q) : (void)0), ...); }
 
 struct Engine {
     int algo = 0, opt_lvl = 0, heur = 0, device = 0, nmaps = 1;
@@ -75,16 +106,30 @@ struct Engine {
     struct GraphSig { DevParams P; float band, delta; int max_iters, grid, follow; };
     GraphSig graph_sig{};
     std::vector<std::pair<int, hipGraphExec_t>> graphs;   // key nr * 256 + nl
-    int relax_kernel(int mode, int k_arg, float rbound, int grid);
+    void relax(int mode, bool dyn, dim3 g, int k_arg, float delta, float rbound, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
+    float band_delta(float scale) const { return delta_abs >= 0.0f ? delta_abs : scale * T * mean_cost; }   // the ordering band
     void finalize_bp(int only_if_done) {   // the back-pointers of the tiles the step touched (k_finalize_bp); MS-DFM level 0 has none (its map has no Info)
-        if (algo == UFM_ALGO_FD) k_finalize_bp<UFM_ALGO_FD><<<2048, 256, 0, stream>>>(P, only_if_done);
-        else if (algo == UFM_ALGO_SG) k_finalize_bp<UFM_ALGO_SG><<<2048, 256, 0, stream>>>(P, only_if_done);
-        else if (opt_lvl >= 1) k_finalize_bp<ALGO_DFM1><<<2048, 256, 0, stream>>>(P, only_if_done);
+        if (algo == UFM_ALGO_DFM && opt_lvl < 1) return;
+        with_lower_op(algo, [&](auto a) { k_finalize_bp<a()><<<2048, 256, 0, stream>>>(P, only_if_done); });
     }
     int tail_grid = 96;              // replan graph: workgroups of the later launches of a phase (few tiles left)
     int replan_graph(int nr, int nl, float band, hipGraphExec_t *out);
     void drop_graphs() { for (auto &g : graphs) hipGraphExecDestroy(g.second); graphs.clear(); }
-    int *h_scratch = nullptr;        // pinned, nmaps*4 ints
+    struct StepScratch {             // pinned: 2 accumulators + 12 * nmaps ints, one allocation carved once (engine_create)
+        unsigned long long *acc = nullptr;     // [2]: engine_set_map's cost sum and count
+        int *consume = nullptr, *init = nullptr, *init_tiles = nullptr;   // [nmaps] each: plan_step's answer per map; the goal tiles of the initialising maps, dense
+        int *goals = nullptr;                  // [2 * nmaps]
+        unsigned int *num_updated = nullptr;   // [nmaps]
+        int *start_el = nullptr;               // [4 * nmaps]
+        float *start_pos = nullptr;            // [2 * nmaps]
+        int carve(int n) {
+            HIPCHK(hipHostMalloc(&acc, 2 * sizeof(unsigned long long) + sizeof(int) * 12 * (size_t)n));
+            consume = reinterpret_cast<int *>(acc + 2); init = consume + n; init_tiles = init + n; goals = init_tiles + n;
+            num_updated = reinterpret_cast<unsigned int *>(goals + 2 * n); start_el = goals + 3 * n;
+            start_pos = reinterpret_cast<float *>(start_el + 4 * n);
+            return UFM_OK;
+        }
+    } scratch;
     int *d_scratch = nullptr;
     uint8_t *d_patch = nullptr;      // staging for host patches
     size_t d_patch_cap = 0;
@@ -101,7 +146,6 @@ struct Engine {
     size_t path_cap = 0;                              // floats per buffer
     std::vector<MapState> maps;
     std::vector<PatchRect> pending;
-    std::vector<PatchRect> region_rects;   // the rectangles the current step consumes (jobs of the block kernel)
     int iter[2] = {0, 0};            // index k of the next relax launch of each queue (never reset: the queues persist)
     bool focused = true;             // stop at the start's key like the reference (end_condition)
     bool start_cell_floor = false;   // start_cell_ = the cell that contains the start position (floor) instead of Cell(Position)'s roundf (Cell.cpp:20-21): what the
@@ -122,12 +166,15 @@ struct Engine {
     float mean_cost = 1.0f;
     int batch_fixed = 0;
     bool profiling = false;
-    std::vector<hipEvent_t> ev;
+    hipEvent_t chain_ev[4] = {nullptr, nullptr, nullptr, nullptr};   // profiling: around the two blind batches of a replan's launch chain
+    std::vector<hipEvent_t> batch_ev;     // ... and the sampled launches of run_phase's batches, batch_ev_slot events per batch in flight
+    int batch_ev_slot = 64;
+    hipEvent_t *batch_event(int slot, int i) { return &batch_ev[(size_t)slot * batch_ev_slot + i]; }
     ufm_stats last{};
 
     int alloc(int width, int length);
     void release();
-    int launch_relax(int mode, float rbound, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
+    void launch_relax(int mode, float rbound, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
     int fetch_counters();
     int wait_published();
     int wait_flag(const unsigned int *flag, unsigned int seq);
@@ -146,7 +193,38 @@ struct Engine {
     int profile_stride = 4;          // profiling: every n-th launch of a plan is bracketed by events
     int reset_queues();
     int read_bounds(float *bmax);
+    // a step (ReplannerBase::step) and its parts, in the order they run; StepRun is what they share
+    struct StepRun {
+        StepPlan plan;
+        ufm_stats st;
+        DevDyn dyn_now;
+        bool dyn_pending;
+        ReplanBegin rb;              // single map: the step bookkeeping and the consumed rectangles of the fused forms
+        float band;                  // margin of the invalidation bound above the start's current key (the key may rise through the patch)
+        int nr, nl;                  // blind batch sizes of a replan
+        int n_init_tiles;
+        uint64_t updated;
+        bool fast_done, skip_raise;  // skip_raise: the block kernel has left nothing to invalidate below its bound (only lowering work beyond the block)
+        std::chrono::steady_clock::time_point t0, t_seed;
+        double u_acc, p_acc;
+    };
+    RouteSwitches route_switches() const {
+        return RouteSwitches{fuse_control, spin_wait, use_region, use_graph, algo != UFM_ALGO_DFM, region_tiles, region_ahead, P.TX, P.TY, nmaps};
+    }
     int step(ufm_stats *out);
+    void flush_dyn(StepRun &r);
+    int begin_step(StepRun &r);
+    void start_elements();
+    StepBegin step_begin_of(int m, int consume, int clear_lmax) const;
+    int replan(StepRun &r);
+    int submit_block(StepRun &r);
+    int continue_block(StepRun &r);
+    int submit_graph(StepRun &r);
+    int submit_chain(StepRun &r);
+    int fused_end(float band);
+    int seed_only(StepRun &r);
+    int converge(StepRun &r);
+    void copy_counters(ufm_stats &st) const;
     int patch(int m, const uint8_t *dev_patch, int x, int y, int w, int h, bool may_defer = false);
     // OPT-IN (ufm_batch_set_param "defer_patches", 1; round 4: it was the default, which silently extended the lifetime the ABI asks of
     // a patch buffer): small patches handed to a batch as device pointers are held back until something needs them applied (the next
@@ -172,7 +250,9 @@ struct Engine {
     int patch_lazy(int m, const uint8_t *host_patch, int x, int y, int w, int h, bool *taken);
     int flush_lazy();
     int ensure_pmask(size_t n);
-    bool region_fits(const int (*rects)[5], int nrect, int m, int *tx0, int *ntx, int *ty0, int *nty) const;
+    void patch_small(int m, const uint8_t *src, int x, int y, int w, int h) {
+        with_elements(algo, [&](auto nodes) { k_patch_small<nodes()><<<1, 1024, 0, stream>>>(P, m, src, d_pmask, x, y, w, h); });
+    }
     // step deltas (ufm_track_changes / ufm_read_changes, ufm_delta.h): nothing below exists unless a caller turned tracking on
     bool track = false;
     float *trk_g = nullptr;          // the baseline: the field as the caller was last told, in the layout of P.G (same gstride)
@@ -185,7 +265,6 @@ struct Engine {
     int track_reset(int m);
     int track_records(size_t cap);
     void track_free();
-    bool lazy_region_ok() const;
 };
 
 void Engine::release() {
@@ -379,23 +458,14 @@ int Engine::wait_flag(const unsigned int *flag, unsigned int seq) {
     return __atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq ? UFM_OK : UFM_ERR_HIP_BASE;
 }
 
-// one relax launch over a short queue (fused triage) with an explicit launch-index argument
-int Engine::relax_kernel(int mode, int k_arg, float rbound, int grid) {
-    const dim3 g(grid), b(NTHR);
-    const float delta = (mode == MODE_RAISE) ? INFINITY : (delta_abs >= 0.0f ? delta_abs : delta_scale * T * mean_cost);
-#define UFM_LAUNCH(A, M) k_relax<A, M, false><<<g, b, 0, stream>>>(P, k_arg, delta, rbound, max_iters)
-    if (mode == MODE_LOWER) {
-        if (algo == UFM_ALGO_FD) UFM_LAUNCH(UFM_ALGO_FD, MODE_LOWER);
-        else if (algo == UFM_ALGO_SG) UFM_LAUNCH(UFM_ALGO_SG, MODE_LOWER);
-        else UFM_LAUNCH(ALGO_DFM1, MODE_LOWER);
-    } else {
-        if (algo == UFM_ALGO_FD) UFM_LAUNCH(UFM_ALGO_FD, MODE_RAISE);
-        else if (algo == UFM_ALGO_SG) UFM_LAUNCH(UFM_ALGO_SG, MODE_RAISE);
-        else if (dfm_follow_info) UFM_LAUNCH(ALGO_DFM1_INFO, MODE_RAISE);
-        else UFM_LAUNCH(ALGO_DFM1, MODE_RAISE);
-    }
-#undef UFM_LAUNCH
-    return UFM_OK;
+// one relax launch: the operator by the planner, the mode, and whether the queue was triaged by k_triage (dyn) or is triaged in the launch (fused)
+void Engine::relax(int mode, bool dyn, dim3 g, int k_arg, float delta, float rbound, hipEvent_t e0, hipEvent_t e1) {
+    auto go = [&](auto a, auto m) {
+        if (dyn) launch(k_relax<a(), m(), true>, g, dim3(NTHR), stream, e0, e1, P, k_arg, delta, rbound, max_iters);
+        else launch(k_relax<a(), m(), false>, g, dim3(NTHR), stream, e0, e1, P, k_arg, delta, rbound, max_iters);
+    };
+    if (mode == MODE_LOWER) with_lower_op(algo, [&](auto a) { go(a, IntC<MODE_LOWER>{}); });
+    else with_raise_op(algo, dfm_follow_info, [&](auto a) { go(a, IntC<MODE_RAISE>{}); });
 }
 // The whole replan submission -- begin, nr invalidation launches, transition, nl lowering
 // launches, end -- captured once per (nr, nl) and replayed: the host enqueues one graph instead of
@@ -404,7 +474,7 @@ int Engine::relax_kernel(int mode, int k_arg, float rbound, int grid) {
 // the per-replan inputs, from host-coherent memory (h_job).
 int Engine::replan_graph(int nr, int nl, float band, hipGraphExec_t *out) {
     GraphSig sig{};
-    sig.P = P; sig.band = band; sig.delta = delta_abs >= 0.0f ? delta_abs : delta_scale * T * mean_cost;
+    sig.P = P; sig.band = band; sig.delta = band_delta(delta_scale);
     sig.max_iters = max_iters; sig.grid = grid_relax * 4096 + tail_grid; sig.follow = dfm_follow_info ? 1 : 0;
     if (std::memcmp(&sig, &graph_sig, sizeof(GraphSig)) != 0) { drop_graphs(); std::memcpy(&graph_sig, &sig, sizeof(GraphSig)); }
     const int key = nr * 256 + nl;
@@ -416,9 +486,9 @@ int Engine::replan_graph(int nr, int nl, float band, hipGraphExec_t *out) {
     // grid, which starts -- and, when the queue has run dry, ends -- sooner (an empty 512-workgroup
     // launch lasts 4.6 us)
     auto grid_of = [&](int i) { return i < 2 ? grid_relax : (i < 4 ? std::max(tail_grid, grid_relax / 2) : tail_grid); };
-    for (int i = 0; i < nr; ++i) relax_kernel(MODE_RAISE, -1 - i, -1.0f, std::min(grid_relax, grid_of(i)));
+    for (int i = 0; i < nr; ++i) relax(MODE_RAISE, false, dim3(std::min(grid_relax, grid_of(i))), -1 - i, INFINITY, -1.0f);
     k_raise_to_lower<<<1, 1024, 0, stream>>>(P, -1);
-    for (int i = 0; i < nl; ++i) relax_kernel(MODE_LOWER, -1 - i, INFINITY, std::min(grid_relax, grid_of(i)));
+    for (int i = 0; i < nl; ++i) relax(MODE_LOWER, false, dim3(std::min(grid_relax, grid_of(i))), -1 - i, band_delta(delta_scale), INFINITY);
     k_replan_end<<<64, T * T, 0, stream>>>(P, -1 - nr, -1 - nl, band, h_ctr, h_flag, 0u);
     finalize_bp(1);     // (behind the publication: the host does not wait for it, the next step's kernels do)
     hipGraph_t g = nullptr;
@@ -433,14 +503,14 @@ int Engine::replan_graph(int nr, int nl, float band, hipGraphExec_t *out) {
     return UFM_OK;
 }
 
-// e0 / e1 (profiling): HIP events recorded on the engine's stream right around the relax kernel
-int Engine::launch_relax(int mode, float rbound, hipEvent_t e0, hipEvent_t e1) {
-    dim3 g(grid_relax), b(NTHR);
+// the next launch of a queue; e0 / e1 (profiling): events attached to the relax kernel's dispatch
+void Engine::launch_relax(int mode, float rbound, hipEvent_t e0, hipEvent_t e1) {
+    dim3 g(grid_relax);
     const int q = (mode == MODE_LOWER) ? Q_LOWER : Q_RAISE;
     // long queue: vectorised triage + balanced hand-out of the released tiles; short queue: fused
     const bool dyn = dynamic_mode && last_active > grid_relax / 4;
     // invalidation is order-free; lowering releases tiles in bands of `delta`
-    const float delta = (mode == MODE_RAISE) ? INFINITY : (delta_abs >= 0.0f ? delta_abs : (dyn ? delta_scale_long : delta_scale) * T * mean_cost);
+    const float delta = (mode == MODE_RAISE) ? INFINITY : band_delta(dyn ? delta_scale_long : delta_scale);
     // a short queue (replans: a handful of tiles per launch) does not need the whole chip: a small
     // grid starts, and when there is nothing left to do ends, sooner
     if (!dyn && last_active <= small_grid / 2 && small_grid < grid_relax) g = dim3(small_grid);
@@ -449,40 +519,10 @@ int Engine::launch_relax(int mode, float rbound, hipEvent_t e0, hipEvent_t e1) {
         if (mode == MODE_LOWER) k_triage<MODE_LOWER><<<64, 256, 0, stream>>>(P, iter[q], delta, rbound);
         else k_triage<MODE_RAISE><<<64, 256, 0, stream>>>(P, iter[q], delta, rbound);
     }
-    // timed launch: the events are attached to the dispatch itself (start / stop time stamps of the
-    // kernel, what rocprofv3 reports too), not recorded around it as separate packets
-    const bool timed = e0 && e1;
-    const int kk = iter[q];
-    const int ms_ = max_iters;
-#define UFM_LAUNCH(A, M) do { \
-        if (timed) { if (dyn) hipExtLaunchKernelGGL((k_relax<A, M, true>), g, b, 0, stream, e0, e1, 0, P, kk, delta, rbound, ms_); \
-                     else hipExtLaunchKernelGGL((k_relax<A, M, false>), g, b, 0, stream, e0, e1, 0, P, kk, delta, rbound, ms_); } \
-        else if (dyn) k_relax<A, M, true><<<g, b, 0, stream>>>(P, kk, delta, rbound, ms_); \
-        else k_relax<A, M, false><<<g, b, 0, stream>>>(P, kk, delta, rbound, ms_); } while (0)
-    if (mode == MODE_LOWER) {
-        if (algo == UFM_ALGO_FD) UFM_LAUNCH(UFM_ALGO_FD, MODE_LOWER);
-        else if (algo == UFM_ALGO_SG) UFM_LAUNCH(UFM_ALGO_SG, MODE_LOWER);
-        else UFM_LAUNCH(ALGO_DFM1, MODE_LOWER);
-    } else {
-        if (algo == UFM_ALGO_FD) UFM_LAUNCH(UFM_ALGO_FD, MODE_RAISE);
-        else if (algo == UFM_ALGO_SG) UFM_LAUNCH(UFM_ALGO_SG, MODE_RAISE);
-        else if (dfm_follow_info) UFM_LAUNCH(ALGO_DFM1_INFO, MODE_RAISE);
-        else UFM_LAUNCH(ALGO_DFM1, MODE_RAISE);
-    }
-#undef UFM_LAUNCH
+    relax(mode, dyn, g, iter[q], delta, rbound, e0, e1);
     ++iter[q];
-    return UFM_OK;
 }
 
-// Launch relax kernels until the active list runs dry.  The list lengths live on
-// the device; the host peeks at them once per batch of launches (an empty launch
-// costs a few microseconds, a host round trip more).
-// A phase also ends when a launch released nothing: everything still queued lies beyond the bound
-// (the start's key) and stays queued for a later step.
-// The host does not wait for a batch before it submits the next one: while it reads the counters batch
-// b published, batch b+1 is already running (a host round trip -- publish, PCIe, decision, first
-// dispatch -- left the GPU idle for ~15 us, 68 times per 4096^2 plan).  The price: when batch b turns
-// out to have drained the queue, batch b+1 consists of launches that find nothing to do (a few us each).
 // A whole lowering phase in one launch: the resident kernel (k_relax<., LOWER, false, 1 | 2>) between the two kernels that
 // move the queue into and out of its per-owner words.  What it leaves behind is an ordinary (short or empty) list
 // for launch iter + 1, which run_phase() then finds.
@@ -493,7 +533,7 @@ int Engine::owned_phase() {
     // visits, 8192^2 36.7 / 35.8 / 35.5 / 36.0 / 37.4, SG 2048^2 5.85 / 5.4 / 5.3 / 5.4 / 5.7; MS-DFM 2048^2 12.0 / 11.8 / 11.4 / 11.7 (2 ... 4); the 8-map
     // MS-DFM batch, bound by the number of visits: 34.0 / 34.3 / 34.9 / 35.8 (2 ... 4)
     const float band_auto = nmaps > 1 ? 2.0f : (algo == UFM_ALGO_DFM ? 3.0f : 2.5f);
-    const float delta = delta_abs >= 0.0f ? delta_abs : (owned_band >= 0.0f ? owned_band : band_auto) * T * mean_cost;
+    const float delta = band_delta(owned_band >= 0.0f ? owned_band : band_auto);
     const double limit_ms = owned_limit_ms >= 0.0f ? (double)owned_limit_ms : 200.0 + (double)P.NT / 250.0;   // (4096^2: 0.46 s; its plan takes 17 ms)
     P.own_limit = (unsigned long long)(limit_ms * 1e5);   // 100 MHz ticks
     P.own_flags = owned_flags;
@@ -506,25 +546,19 @@ int Engine::owned_phase() {
     // where there are always more tiles to visit than workgroups (several maps, or a front as long as that of an 8192^2 map); a single
     // 4096^2 plan is bound by the chain of dependent visits along the front's way, not by their number
     const dim3 g(P.own_nw), b(half ? NTHR / 2 : NTHR);
-    const int ms_ = max_iters;
     own_timed = false;
     if (profiling) {
         for (auto &e : own_ev) if (!e) HIPCHK(hipEventCreate(&e));
         own_timed = true;
     }
+    hipEvent_t e0 = own_timed ? own_ev[0] : nullptr, e1 = own_timed ? own_ev[1] : nullptr;
+    with_lower_op(algo, [&](auto a) {
 #if UFM_TILE == 16
-#define UFM_LAUNCH(A) do { if (own_timed) { if (half) hipExtLaunchKernelGGL((k_relax<A, MODE_LOWER, false, 2>), g, b, 0, stream, own_ev[0], own_ev[1], 0, P, k, delta, INFINITY, ms_); \
-                                                else hipExtLaunchKernelGGL((k_relax<A, MODE_LOWER, false, 1>), g, b, 0, stream, own_ev[0], own_ev[1], 0, P, k, delta, INFINITY, ms_); } \
-                           else if (half) k_relax<A, MODE_LOWER, false, 2><<<g, b, 0, stream>>>(P, k, delta, INFINITY, ms_); \
-                           else k_relax<A, MODE_LOWER, false, 1><<<g, b, 0, stream>>>(P, k, delta, INFINITY, ms_); } while (0)
-#else   // 32 x 32 tiles: the 16-wave form only (the skewed 8-wave patch map is written for 4 x 4 patches per tile)
-#define UFM_LAUNCH(A) do { if (own_timed) hipExtLaunchKernelGGL((k_relax<A, MODE_LOWER, false, 1>), g, b, 0, stream, own_ev[0], own_ev[1], 0, P, k, delta, INFINITY, ms_); \
-                           else k_relax<A, MODE_LOWER, false, 1><<<g, b, 0, stream>>>(P, k, delta, INFINITY, ms_); } while (0)
-#endif
-    if (algo == UFM_ALGO_FD) UFM_LAUNCH(UFM_ALGO_FD);
-    else if (algo == UFM_ALGO_SG) UFM_LAUNCH(UFM_ALGO_SG);
-    else UFM_LAUNCH(ALGO_DFM1);
-#undef UFM_LAUNCH
+        if (half) launch(k_relax<a(), MODE_LOWER, false, 2>, g, b, stream, e0, e1, P, k, delta, INFINITY, max_iters);
+        else
+#endif      // (32 x 32 tiles: the 16-wave form only -- the skewed 8-wave patch map is written for 4 x 4 patches per tile)
+        launch(k_relax<a(), MODE_LOWER, false, 1>, g, b, stream, e0, e1, P, k, delta, INFINITY, max_iters);
+    });
     k_own_export<<<256, 256, 0, stream>>>(P, k + 1);
     HIPCHK(hipGetLastError());
     ++iter[Q_LOWER];
@@ -533,91 +567,70 @@ int Engine::owned_phase() {
     return UFM_OK;
 }
 
+// Launch relax kernels until the active list runs dry.  The list lengths live on
+// the device; the host peeks at them once per batch of launches (an empty launch
+// costs a few microseconds, a host round trip more).
+// A phase also ends when a launch released nothing: everything still queued lies beyond the bound
+// (the start's key) and stays queued for a later step.
+// The host does not wait for a batch before it submits the next one: while it reads the counters batch
+// b published, batch b+1 is already running (a host round trip -- publish, PCIe, decision, first
+// dispatch -- left the GPU idle for ~15 us, 68 times per 4096^2 plan).  The price: when batch b turns
+// out to have drained the queue, batch b+1 consists of launches that find nothing to do (a few us each).
 int Engine::run_phase(int mode, float rbound, uint32_t *launches, float *kernel_ms, uint32_t *timed) {
     const int q = (mode == MODE_LOWER) ? Q_LOWER : Q_RAISE;
-    int batch = batch_fixed > 0 ? batch_fixed : 4;
     const long cap = 64L * (P.TX + P.TY) * T + 4096;   // generous bound on sweeps
+    // pipelined: batch b + 1 is submitted before the counters batch b published are looked at; otherwise the host waits for every batch
+    const bool pipelined = spin_wait && pipeline_batches && h_pipe_ctr[0];
+    batch_ev_slot = 2 * std::max(32, batch_fixed);     // events per batch: two per launch (adaptive batches: <= 32 launches)
+    while (profiling && batch_ev.size() < (size_t)((pipelined ? 2 : 1) * batch_ev_slot)) { hipEvent_t a; HIPCHK(hipEventCreate(&a)); batch_ev.push_back(a); }
+    struct Batch { unsigned int seq; int slot, ns, iter_after; };
+    auto counters = [&](const Batch &b) -> const DevCounters * { return pipelined ? h_pipe_ctr[b.slot] : h_ctr; };
     long total = 0;
-    if (spin_wait && pipeline_batches && h_pipe_ctr[0]) {
-        struct InFlight { unsigned int seq; int slot, ns, iter_after; };
-        const int EVSLOT = 2 * std::max(32, batch_fixed);   // events per slot: two per launch of a batch (adaptive batches: <= 32 launches)
-        while (profiling && ev.size() < (size_t)(4 + 2 * EVSLOT)) { hipEvent_t a; HIPCHK(hipEventCreate(&a)); ev.push_back(a); }
-        auto collect = [&](const InFlight &f) -> int {  // wait for the batch, add its timed launches
-            int rc = wait_flag(h_pipe_flag[f.slot], f.seq);
-            if (rc != UFM_OK) return rc;
-            for (int k = 0; k < f.ns; ++k) {
-                float ms = 0;
-                HIPCHK(hipEventElapsedTime(&ms, ev[4 + f.slot * EVSLOT + 2 * k], ev[4 + f.slot * EVSLOT + 2 * k + 1]));
-                *kernel_ms += ms;
-            }
-            *timed += (uint32_t)f.ns;
-            return UFM_OK;
-        };
-        InFlight prev{}, cur{};
-        bool have_prev = false;
-        int slot = 0;
-        for (;;) {
-            int ns = 0;
-            for (int k = 0; k < batch; ++k) {
-                const bool timed_k = profiling && ((total + k) % profile_stride == 0);
-                const int eb = 4 + slot * EVSLOT + 2 * ns;
-                launch_relax(mode, rbound, timed_k ? ev[eb] : nullptr, timed_k ? ev[eb + 1] : nullptr);
-                if (timed_k) ++ns;
-            }
-            ++pub_seq;
-            k_publish<<<1, 64, 0, stream>>>(P.ctr, h_pipe_ctr[slot], h_pipe_flag[slot], pub_seq);
-            HIPCHK(hipGetLastError());
-            cur = {pub_seq, slot, ns, iter[q]};
-            *launches += (uint32_t)batch;
-            total += batch;
-            if (have_prev) {
-                int rc = collect(prev);
-                if (rc != UFM_OK) return rc;
-                const DevCounters *c = h_pipe_ctr[prev.slot];
-                const int active = c->cnt[q][prev.iter_after % 3];
-                const bool done = active == 0 || c->rel[q][(prev.iter_after + 2) % 3] == 0;   // drained / nothing released: the rest lies beyond the bound
-                if (done || total > cap) {
-                    rc = collect(cur);                  // the batch submitted meanwhile found nothing to do
-                    if (rc != UFM_OK) return rc;
-                    last_active = h_pipe_ctr[cur.slot]->cnt[q][cur.iter_after % 3];
-                    return done ? UFM_OK : UFM_ERR_NOT_CONVERGED;
-                }
-                last_active = active;
-                batch = batch_fixed > 0 ? batch_fixed : (active > 512 ? 32 : (active > 256 ? 16 : (active > 32 ? 8 : 4)));
-            }
-            prev = cur; have_prev = true; slot ^= 1;
-        }
-    }
-    for (;;) {
-        int ns = 0;   // launches of this batch that are timed: a sample, the event packets cost ~4 us each
-        for (int k = 0; k < batch; ++k) {
+    auto submit = [&](int n, int slot, Batch *b) -> int {     // one batch with its sampled events (the event packets cost ~4 us each)
+        int ns = 0;
+        for (int k = 0; k < n; ++k) {
             const bool timed_k = profiling && ((total + k) % profile_stride == 0);
-            if (timed_k) {
-                while (ev.size() < (size_t)(2 * (ns + 1) + 4)) {   // ev[0..3] belong to the replan path
-                    hipEvent_t a;
-                    HIPCHK(hipEventCreate(&a));
-                    ev.push_back(a);
-                }
-            }
-            launch_relax(mode, rbound, timed_k ? ev[4 + 2 * ns] : nullptr, timed_k ? ev[4 + 2 * ns + 1] : nullptr);
+            launch_relax(mode, rbound, timed_k ? *batch_event(slot, 2 * ns) : nullptr, timed_k ? *batch_event(slot, 2 * ns + 1) : nullptr);
             if (timed_k) ++ns;
         }
+        if (pipelined) k_publish<<<1, 64, 0, stream>>>(P.ctr, h_pipe_ctr[slot], h_pipe_flag[slot], ++pub_seq);
         HIPCHK(hipGetLastError());
-        *launches += (uint32_t)batch;
-        total += batch;
-        { int rc = fetch_counters(); if (rc != UFM_OK) return rc; }
-        for (int k = 0; k < ns; ++k) {
+        *b = {pub_seq, slot, ns, iter[q]};
+        *launches += (uint32_t)n;
+        total += n;
+        return UFM_OK;
+    };
+    auto collect = [&](const Batch &b) -> int {               // wait for the batch's counters, add its timed launches
+        int rc = pipelined ? wait_flag(h_pipe_flag[b.slot], b.seq) : fetch_counters();
+        if (rc != UFM_OK) return rc;
+        for (int k = 0; k < b.ns; ++k) {
             float ms = 0;
-            HIPCHK(hipEventElapsedTime(&ms, ev[4 + 2 * k], ev[4 + 2 * k + 1]));
+            HIPCHK(hipEventElapsedTime(&ms, *batch_event(b.slot, 2 * k), *batch_event(b.slot, 2 * k + 1)));
             *kernel_ms += ms;
         }
-        *timed += (uint32_t)ns;
-        const int active = h_ctr->cnt[q][iter[q] % 3];
+        *timed += (uint32_t)b.ns;
+        return UFM_OK;
+    };
+    Batch prev{}, cur{};
+    int batch = batch_fixed > 0 ? batch_fixed : 4;
+    for (bool first = true;; first = false) {
+        { int rc = submit(batch, pipelined ? (prev.slot ^ (first ? 0 : 1)) : 0, &cur); if (rc != UFM_OK) return rc; }
+        if (pipelined && first) { prev = cur; continue; }
+        const Batch &look = pipelined ? prev : cur;           // the batch whose counters decide
+        { int rc = collect(look); if (rc != UFM_OK) return rc; }
+        const int active = counters(look)->cnt[q][look.iter_after % 3];
+        const bool done = active == 0 || counters(look)->rel[q][(look.iter_after + 2) % 3] == 0;   // drained / nothing released: the rest lies beyond the bound
         last_active = active;
-        if (active == 0) return UFM_OK;
-        if (h_ctr->rel[q][(iter[q] + 2) % 3] == 0) return UFM_OK;   // the last launch released nothing
-        if (total > cap) return UFM_ERR_NOT_CONVERGED;
+        if (done || total > cap) {
+            if (pipelined) {                                  // the batch submitted meanwhile found nothing to do
+                int rc = collect(cur);
+                if (rc != UFM_OK) return rc;
+                last_active = counters(cur)->cnt[q][cur.iter_after % 3];
+            }
+            return done ? UFM_OK : UFM_ERR_NOT_CONVERGED;
+        }
         batch = batch_fixed > 0 ? batch_fixed : (active > 512 ? 32 : (active > 256 ? 16 : (active > 32 ? 8 : 4)));
+        prev = cur;
     }
 }
 
@@ -631,12 +644,11 @@ int Engine::flush_deferred_only() {
     a.n = (int)deferred.size();
     for (int i = 0; i < a.n; ++i) {
         const DeferredPatch &d = deferred[i];
-        int *q = a.rect[i]; q[0] = d.m; q[1] = d.x; q[2] = d.y; q[3] = d.w; q[4] = d.h;
+        put_rect(a.rect[i], PatchRect{d.m, d.x, d.y, d.w, d.h});
         a.ptr[i] = d.ptr;
     }
     deferred.clear();
-    if (algo == UFM_ALGO_DFM) k_patch_multi<false><<<a.n, 1024, 0, stream>>>(P, a, d_pmask);
-    else k_patch_multi<true><<<a.n, 1024, 0, stream>>>(P, a, d_pmask);
+    with_elements(algo, [&](auto nodes) { k_patch_multi<nodes()><<<a.n, 1024, 0, stream>>>(P, a, d_pmask); });
     HIPCHK(hipGetLastError());
     return UFM_OK;
 }
@@ -645,9 +657,7 @@ int Engine::ensure_pmask(size_t n) {   // room for the masks of PATCH_MULTI smal
     const size_t need = std::max((size_t)PATCH_MULTI * 4096, n);
     if (need > d_pmask_cap) {
         { int rc = flush_deferred_only(); if (rc != UFM_OK) return rc; }      // (their launch writes the old buffer)
-        if (d_pmask) { HIPCHK(hipStreamSynchronize(stream)); hipFree(d_pmask); d_pmask = nullptr; d_pmask_cap = 0; }
-        HIPCHK(hipMalloc(&d_pmask, need));
-        d_pmask_cap = need;
+        { int rc = regrow(stream, need, d_pmask_cap, need, d_pmask); if (rc != UFM_OK) return rc; }
     }
     return UFM_OK;
 }
@@ -656,9 +666,7 @@ int Engine::flush_lazy() {
     if (lazy.empty()) return UFM_OK;
     { int rc = ensure_pmask(4096); if (rc != UFM_OK) return rc; }
     for (const LazyPatch &p : lazy) {
-        const uint8_t *src = h_lazy + (size_t)p.slot * 4096;
-        if (algo == UFM_ALGO_DFM) k_patch_small<false><<<1, 1024, 0, stream>>>(P, p.m, src, d_pmask, p.x, p.y, p.w, p.h);
-        else k_patch_small<true><<<1, 1024, 0, stream>>>(P, p.m, src, d_pmask, p.x, p.y, p.w, p.h);
+        patch_small(p.m, h_lazy + (size_t)p.slot * 4096, p.x, p.y, p.w, p.h);
         lazy_dirty[p.slot] = true;         // (read by a kernel that is only queued: patch_lazy waits for the stream before it writes the slot again)
     }
     lazy.clear();
@@ -685,44 +693,6 @@ int Engine::patch_lazy(int m, const uint8_t *host_patch, int x, int y, int w, in
     *taken = true;
     return UFM_OK;
 }
-// the block of the replan kernel around a set of consumed rectangles {map, x, y, w, h}: its goal-side edge `region_ahead` tiles beyond the
-// rectangles' centre, the rest of its extent behind it -- where the elements that lean on the patched cells are; false if they do not fit into one block
-bool Engine::region_fits(const int (*rects)[5], int nrect, int m, int *tx0, int *ntx, int *ty0, int *nty) const {
-    if (nrect <= 0) return false;
-    const bool nodes = algo != UFM_ALGO_DFM;
-    int ex0 = INT32_MAX, ex1 = -1, ey0 = INT32_MAX, ey1 = -1;
-    for (int r = 0; r < nrect; ++r) {
-        const int *qr = rects[r];
-        ex0 = std::min(ex0, qr[1]); ex1 = std::max(ex1, qr[1] + qr[4] - (nodes ? 0 : 1));
-        ey0 = std::min(ey0, qr[2]); ey1 = std::max(ey1, qr[2] + qr[3] - (nodes ? 0 : 1));
-    }
-    auto place = [&](int e0, int e1, int goal_e, int ntiles_map, int *t0, int *nt) {
-        *nt = std::min(std::min(region_tiles, RTMAX), ntiles_map);
-        const int tc = ((e0 + e1) / 2) / T;
-        int lo = (goal_e >= (e0 + e1) / 2) ? tc + region_ahead - *nt + 1 : tc - region_ahead;
-        lo = std::max(0, std::min(lo, ntiles_map - *nt));
-        *t0 = lo;
-        return e0 / T >= lo && e1 / T <= lo + *nt - 1;      // every consumed rectangle inside the block
-    };
-    const bool okx = place(ex0, ex1, maps[m].goal_ex, P.TX, tx0, ntx);
-    const bool oky = place(ey0, ey1, maps[m].goal_ey, P.TY, ty0, nty);
-    return okx && oky;
-}
-// will the next step() send the pending patches (the held ones among them) through the block kernel?  The conditions of step()'s fast path.
-bool Engine::lazy_region_ok() const {
-    if (!(nmaps == 1 && fuse_control && spin_wait && use_region)) return false;
-    const MapState &ms = maps[0];
-    if (!ms.have_map || !ms.goal_set || ms.initialize_search || ms.new_goal || !ms.new_start) return false;
-    if (pending.empty() || pending.size() > 4) return false;
-    int rects[4][5], n = 0;
-    for (const PatchRect &r : pending) {
-        if ((r.w + 1) * (r.h + 1) > 65 * 65) return false;
-        int *q = rects[n++]; q[0] = r.m; q[1] = r.x; q[2] = r.y; q[3] = r.w; q[4] = r.h;
-    }
-    int a, b, c, d;
-    return region_fits(rects, n, 0, &a, &b, &c, &d);
-}
-
 int Engine::patch(int m, const uint8_t *dev_patch, int x, int y, int w, int h, bool may_defer) {
     if (m < 0 || m >= nmaps || !allocated || !maps[m].have_map) return UFM_ERR_INVALID;
     if (x < 0 || y < 0 || w <= 0 || h <= 0 || x + h > L || y + w > W) return UFM_ERR_INVALID;   // Graph.cpp:38-41
@@ -742,486 +712,456 @@ int Engine::patch(int m, const uint8_t *dev_patch, int x, int y, int w, int h, b
     }
     { int rc = flush_deferred(); if (rc != UFM_OK) return rc; }   // keep the order of the patches
     if (n <= 4096) {
-        if (algo == UFM_ALGO_DFM) k_patch_small<false><<<1, 1024, 0, stream>>>(P, m, dev_patch, d_pmask, x, y, w, h);
-        else k_patch_small<true><<<1, 1024, 0, stream>>>(P, m, dev_patch, d_pmask, x, y, w, h);
+        patch_small(m, dev_patch, x, y, w, h);
     } else {
         k_patch_apply<<<(n + 255) / 256, 256, 0, stream>>>(P, m, dev_patch, d_pmask, x, y, w, h);
         const int ne = (w + 1) * (h + 1);
-        if (algo == UFM_ALGO_DFM) k_patch_seed<false><<<(ne + 255) / 256, 256, 0, stream>>>(P, m, d_pmask, x, y, w, h);
-        else k_patch_seed<true><<<(ne + 255) / 256, 256, 0, stream>>>(P, m, d_pmask, x, y, w, h);
+        with_elements(algo, [&](auto nodes) { k_patch_seed<nodes()><<<(ne + 255) / 256, 256, 0, stream>>>(P, m, d_pmask, x, y, w, h); });
     }
     HIPCHK(hipGetLastError());
     pending.push_back({m, x, y, w, h});
     return UFM_OK;
 }
 
-int Engine::step(ufm_stats *out) {
-    // ReplannerBase.h:44-45
-    for (int m = 0; m < nmaps; ++m) if (!maps[m].have_map) return UFM_LOOP_FAILURE_NO_GRAPH;
-    for (int m = 0; m < nmaps; ++m) if (!maps[m].goal_set) return UFM_LOOP_FAILURE_NO_GOAL;
-    ufm_stats st{};
-    const auto t0 = std::chrono::steady_clock::now();
+// ---- a step: ReplannerBase::step (ReplannerBase.h:43-75) --------------------------------------------------------------------
+// plan_step (ufm_route.h) says what the step is and which route a replan takes; the parts below act on that, in the order they are written.
+
+// heuristic multiplier / threshold / focused flag live in device memory (DevDyn); a changed value reaches the
+// device with the first kernel of the step: through the job record of the block kernel or of the graph, or here by k_set_dyn
+void Engine::flush_dyn(StepRun &r) {
+    if (!r.dyn_pending) return;
+    k_set_dyn<<<1, 1, 0, stream>>>(P.dyn, r.dyn_now);
+    dyn_dev = r.dyn_now; r.dyn_pending = false;
+}
+
+// start elements: the 4 corners of the start cell (FD impl:9-13, Cell.cpp:48-60) / the start cell (DFM)
+void Engine::start_elements() {
+    for (int m = 0; m < nmaps; ++m) {
+        const MapState &ms = maps[m];
+        int *st_el = scratch.start_el + 4 * m;
+        float *sp = scratch.start_pos + 2 * m;
+        for (int i = 0; i < 4; ++i) st_el[i] = -1;
+        sp[0] = sp[1] = 0.0f;
+        if (!ms.start_set) continue;
+        const int cx = (int)(start_cell_floor ? std::floor(ms.start_x) : std::roundf(ms.start_x)), cy = (int)(start_cell_floor ? std::floor(ms.start_y) : std::roundf(ms.start_y));
+        // keys measure from start_pos_ (FD/SG, Position::distance) or from start_cell_ (DFM, Cell::distance)
+        sp[0] = (algo == UFM_ALGO_DFM) ? (float)cx : ms.start_x;
+        sp[1] = (algo == UFM_ALGO_DFM) ? (float)cy : ms.start_y;
+        const int ncorner = (algo == UFM_ALGO_DFM) ? 1 : 4;
+        for (int i = 0; i < ncorner; ++i) {
+            const int ex = cx + (i & 1), ey = cy + (i >> 1);
+            if (ex >= 0 && ey >= 0 && ex < P.EX && ey < P.EY) st_el[i] = ex * P.EY + ey;
+        }
+    }
+}
+StepBegin Engine::step_begin_of(int m, int consume, int clear_lmax) const {
+    StepBegin sb{};
+    for (int i = 0; i < 4; ++i) sb.start[i] = scratch.start_el[4 * m + i];
+    sb.consume = consume; sb.clear_lmax = clear_lmax;
+    sb.sx = scratch.start_pos[2 * m]; sb.sy = scratch.start_pos[2 * m + 1];
+    return sb;
+}
+
+// Everything in front of the step's submission: the held patches, the batch's counters, the initialising maps' fills and goals, the
+// start elements, and the consumed rectangles -- their marks cleared, or handed to the fused forms in r.rb
+int Engine::begin_step(StepRun &r) {
+    const StepPlan &pl = r.plan;
     const bool single = (nmaps == 1);
     // held host patches: the replan's block kernel applies them itself if this step goes that way; otherwise now, the ordinary way
-    const bool lazy_in_kernel = !lazy.empty() && lazy_region_ok();
-    if (!lazy_in_kernel) { int rc = flush_deferred(); if (rc != UFM_OK) return rc; }   // (and a batch's deferred device patches: one launch)
-
+    if (!pl.held_in_kernel) { int rc = flush_deferred(); if (rc != UFM_OK) return rc; }   // (and a batch's deferred device patches: one launch)
     if (!single) {
         HIPCHK(hipMemsetAsync(&P.ctr->tcount, 0, sizeof(int), stream));
         HIPCHK(hipMemsetAsync(&P.ctr->expanded, 0, 4 * sizeof(unsigned long long), stream));
         HIPCHK(hipMemsetAsync(&P.ctr->raise_visits, 0, sizeof(unsigned long long), stream));
         if (profiling) HIPCHK(hipMemsetAsync(P.lmax, 0, sizeof(int) * LMAX, stream));
     }
-    // heuristic multiplier / threshold / focused flag live in device memory (DevDyn); a changed value reaches the
-    // device with the first kernel of the step: through the replan graph's job record, or by k_set_dyn
-    const DevDyn dyn_now{heur ? heuristic_multiplier : 0.0f, thr_uchar, focused ? 1 : 0, 0};
-    bool dyn_pending = std::memcmp(&dyn_now, &dyn_dev, sizeof(DevDyn)) != 0;
-    auto flush_dyn = [&]() {
-        if (!dyn_pending) return;
-        k_set_dyn<<<1, 1, 0, stream>>>(P.dyn, dyn_now);
-        dyn_dev = dyn_now; dyn_pending = false;
-    };
-
-    // classify maps: (re)initialise, propagate pending patches, or idle  (ReplannerBase.h:48-59)
-    int n_init = 0, n_upd = 0;
-    int *consume = h_scratch, *init_tiles = h_scratch + nmaps, *goals = h_scratch + 2 * nmaps;
-    {   // a full re-initialisation drops whatever the old search left queued
-        bool all_init = true;
-        for (int m = 0; m < nmaps; ++m) all_init = all_init && (maps[m].initialize_search || maps[m].new_goal);
-        if (all_init) { int rc = reset_queues(); if (rc != UFM_OK) return rc; }
-    }
+    // a full re-initialisation drops whatever the old search left queued
+    if (pl.n_init == nmaps) { int rc = reset_queues(); if (rc != UFM_OK) return rc; }
     for (int m = 0; m < nmaps; ++m) {
         MapState &ms = maps[m];
-        consume[m] = 0;
-        if (ms.initialize_search || ms.new_goal) {
-            consume[m] = 1;
-            goals[2 * m] = ms.goal_elem_valid ? ms.goal_ex : -1;
-            goals[2 * m + 1] = ms.goal_elem_valid ? ms.goal_ey : -1;
-            k_fill<<<1024, 256, 0, stream>>>(P.G + (size_t)m * P.gstride, P.gstride, INFINITY);
-            HIPCHK(hipMemsetAsync(P.bp + (size_t)m * P.gstride, BP_NONE, P.gstride, stream));
-            k_fill<<<256, 256, 0, stream>>>(P.ring + (size_t)m * P.NTm * RING, (size_t)P.NTm * RING, INFINITY);
-            if (ms.goal_elem_valid) init_tiles[n_init++] = m * P.NTm + (ms.goal_ex / T) * P.TY + (ms.goal_ey / T);
-            else ++n_init;   // nothing reachable: field stays +inf
-        } else if (ms.new_start) {
-            ms.new_start = false;
-            consume[m] = 1;
-            ++n_upd;
-        }
+        if (!scratch.init[m]) { if (scratch.consume[m]) ms.new_start = false; continue; }
+        scratch.goals[2 * m] = ms.goal_elem_valid ? ms.goal_ex : -1;
+        scratch.goals[2 * m + 1] = ms.goal_elem_valid ? ms.goal_ey : -1;
+        k_fill<<<1024, 256, 0, stream>>>(P.G + (size_t)m * P.gstride, P.gstride, INFINITY);
+        HIPCHK(hipMemsetAsync(P.bp + (size_t)m * P.gstride, BP_NONE, P.gstride, stream));
+        k_fill<<<256, 256, 0, stream>>>(P.ring + (size_t)m * P.NTm * RING, (size_t)P.NTm * RING, INFINITY);
+        // (a goal outside the map: nothing reachable, the field stays +inf -- the map initialises, the list does not get a tile)
+        if (ms.goal_elem_valid) scratch.init_tiles[r.n_init_tiles++] = m * P.NTm + (ms.goal_ex / T) * P.TY + (ms.goal_ey / T);
     }
     // (goal array upload is per map to keep untouched maps' goals)
+    for (int m = 0; m < nmaps; ++m)
+        if (scratch.init[m]) HIPCHK(hipMemcpyAsync(P.goal + 2 * m, scratch.goals + 2 * m, 2 * sizeof(int), hipMemcpyHostToDevice, stream));
+    start_elements();
+    if (single) {
+        r.rb.sb = step_begin_of(0, scratch.consume[0], profiling ? 1 : 0);
+        if (!pl.fused) k_step_begin<<<1, 256, 0, stream>>>(P, r.rb.sb);
+    } else {
+        HIPCHK(hipMemcpyAsync(P.start, scratch.start_el, sizeof(int) * 4 * nmaps, hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(P.spos, scratch.start_pos, sizeof(float) * 2 * nmaps, hipMemcpyHostToDevice, stream));
+    }
+    if (pl.n_upd > 0 || pl.n_init > 0) {
+        if (!single) HIPCHK(hipMemcpyAsync(P.consume, scratch.consume, sizeof(int) * nmaps, hipMemcpyHostToDevice, stream));
+        // consume the pending patch rectangles of the participating maps, keep the others
+        size_t kept = 0;
+        for (const PatchRect &p : pending) {
+            if (!scratch.consume[p.m]) { pending[kept++] = p; continue; }
+            const int cnt = (p.h + 1) * (p.w + 1);
+            if (pl.fused) put_rect(r.rb.rect[r.rb.nrect++], p);
+            else k_clear_marks<<<(cnt + 255) / 256, 256, 0, stream>>>(P, p.m, p.x, p.y, p.w, p.h);
+        }
+        pending.resize(kept);
+    }
+    return UFM_OK;
+}
+
+// the device-side end check of a fused submission (k_replan_end publishes the counters), the back-pointers behind it
+int Engine::fused_end(float band) {
+    ++pub_seq;
+    k_replan_end<<<64, T * T, 0, stream>>>(P, iter[Q_RAISE], iter[Q_LOWER], band, h_ctr, h_flag, pub_seq);
+    finalize_bp(1);     // (behind the publication: the host does not wait for it, the next step's kernels do)
+    HIPCHK(hipGetLastError());
+    return wait_published();
+}
+
+// Route::BlockSingle / BlockBatch: one workgroup per job runs both phases in LDS on the block plan_step placed (ufm_region.h)
+int Engine::submit_block(StepRun &r) {
+    const StepPlan &pl = r.plan;
+    const bool batch = pl.route == Route::BlockBatch;
+    RegionJobs rjs{};
+    rjs.n = pl.njobs;
+    const unsigned int seq = ++pub_seq;
+    for (int i = 0; i < pl.njobs; ++i) {
+        const RouteJob &pj = pl.job[i];
+        RegionJob &j = rjs.j[i];
+        if (batch) {       // (the host has done the step bookkeeping of a batch: k_step_begin's part is the job's alone)
+            j.rb.sb = step_begin_of(pj.map, 1, 0);
+            j.rb.nrect = pj.nrect;
+            std::memcpy(j.rb.rect, pj.rect, sizeof(pj.rect));
+        } else {
+            j.rb = r.rb;
+        }
+        j.rb.k_raise = iter[Q_RAISE]; j.rb.band = r.band;
+        j.tx0 = pj.tx0; j.ntx = pj.ntx; j.ty0 = pj.ty0; j.nty = pj.nty;
+        j.dyn = r.dyn_now; j.k_lower = iter[Q_LOWER]; j.max_sweeps = region_sweeps; j.debug = region_debug;
+        j.slack = 255.0f * SQRT2F + 1.0f;     // the largest cost of one move (a diagonal through the most expensive cell)
+        j.delta = region_band > 0.0f ? region_band * 4.0f * mean_cost : INFINITY;
+        j.map = pj.map; j.batch = batch ? 1 : 0; j.seq = seq;
+    }
+    if (pl.held_in_kernel) {                        // the held host patches are the last rectangles: the kernel applies them
+        const int first = r.rb.nrect - (int)lazy.size();
+        for (size_t i = 0; i < lazy.size(); ++i) rjs.j[0].psrc[first + (int)i] = h_lazy + (size_t)lazy[i].slot * 4096;
+        lazy.clear();                               // (the kernel has read them when this step returns: the slots are free again then)
+    }
+    if (batch) {   // the counters the maps' workgroups add to
+        HIPCHK(hipMemsetAsync(&P.ctr->rbound, 0, offsetof(DevCounters, done_fail) + sizeof(int) - offsetof(DevCounters, rbound), stream));
+        k_fill<<<1, 64, 0, stream>>>(reinterpret_cast<float *>(&P.ctr->qmin[Q_RAISE]), (size_t)1, INFINITY);
+    }
+    // the per-step scalars: a single map's workgroup stores the job's copy itself (it is the only reader before the next launch); a batch's
+    // workgroups read *P.dyn side by side (start_bound, tile_heuristic), so there it is in place before the launch
+    if (batch) flush_dyn(r);
+    else { dyn_dev = r.dyn_now; r.dyn_pending = false; }
+    const bool reg_timed = profiling && (region_runs & 7u) == 0u;     // a sample: the event packets cost a few microseconds each
+    if (reg_timed) for (auto &e : reg_ev) if (!e) HIPCHK(hipEventCreate(&e));
+    with_raise_op(algo, dfm_follow_info, [&](auto a) {
+        launch(k_replan_region<a()>, dim3(rjs.n), dim3(NTHR), stream, reg_timed ? reg_ev[0] : nullptr, reg_timed ? reg_ev[1] : nullptr, P, rjs, h_ctr, h_flag);
+    });
+    HIPCHK(hipGetLastError());
+    last_active = 1;
+    { int rc = wait_published(); if (rc != UFM_OK) return rc; }
+    ufm_stats &st = r.st;
+    st.region_launches = 1u;
+    for (int i = 0; i < rjs.n; ++i) st.region_tiles += (uint32_t)(rjs.j[i].ntx * rjs.j[i].nty);
+    if (reg_timed) {      // (the kernel has published its result: its stop event follows within microseconds -- spin, do not sleep)
+        hipError_t q;
+        while ((q = hipEventQuery(reg_ev[1])) == hipErrorNotReady) __builtin_ia32_pause();
+        HIPCHK(q);
+        HIPCHK(hipEventElapsedTime(&st.region_kernel_ms, reg_ev[0], reg_ev[1]));
+        st.region_timed = 1u;
+    }
+    region_runs += (uint32_t)rjs.n;
+    if (h_ctr->done) region_done += (uint32_t)rjs.n;
+    else if (focused) {
+        // (its end check has the smallest invalidation priority of the map -- of any map of a batch --, queued or parked: at or
+        //  beyond the bound -- a batch: the largest of the maps' bounds -- means the launch chain's invalidation phase, two batches
+        //  of launches and two host round trips, would release nothing)
+        float qm;
+        std::memcpy(&qm, &h_ctr->qmin[Q_RAISE], sizeof(float));
+        r.skip_raise = !(qm < h_ctr->rbound);
+    }
+    return UFM_OK;
+}
+
+// The block kernel has left work beyond its block (3 of the headline's 100 replans; a round of a batch as soon as ONE of its maps
+// has): the launch chain takes over from the queues -- first as ONE blind submission ending in the device-side end check, like
+// the fused chain (a few launches that may find nothing to do are cheaper than the adaptive loop's host round trips:
+// that loop cost a batch round of config 4 ~0.6 ms), and only if that was not enough through converge().
+int Engine::continue_block(StepRun &r) {
+    // (one invalidation launch even when the block kernel saw nothing to invalidate below its bound: the end check reads what the
+    //  last launch of each phase released)
+    const int nr2 = r.skip_raise ? 1 : std::max(1, cont_raise), nl2 = cont_lower;
+    last_active = 1;
+    k_unpark<<<1, 1024, 0, stream>>>(P, Q_RAISE, iter[Q_RAISE], -1.0f);       // (-1: the bound the block kernel left in the counters)
+    for (int i = 0; i < nr2; ++i) launch_relax(MODE_RAISE, -1.0f);
+    k_raise_to_lower<<<1, 1024, 0, stream>>>(P, iter[Q_LOWER]);
+    for (int i = 0; i < nl2; ++i) launch_relax(MODE_LOWER, INFINITY);
+    { int rc = fused_end(r.band); if (rc != UFM_OK) return rc; }
+    r.fast_done = h_ctr->done != 0;
+    r.st.raise_launches += (uint32_t)nr2;
+    r.st.launches += (uint32_t)(nr2 + nl2);
+    r.skip_raise = false;
+    ++region_cont; if (r.fast_done) ++region_cont_done;
+    return UFM_OK;
+}
+
+// Route::Graph: the fused chain, captured once per (nr, nl) and replayed; its inputs go through the job record
+int Engine::submit_graph(StepRun &r) {
+    r.rb.k_raise = iter[Q_RAISE]; r.rb.band = r.band;
+    hipGraphExec_t ge = nullptr;
+    { int rc = replan_graph(r.nr, r.nl, r.band, &ge); if (rc != UFM_OK) return rc; }
+    h_job->rb = r.rb; h_job->k_lower = iter[Q_LOWER]; h_job->seq = ++pub_seq;
+    h_job->dyn = r.dyn_now; dyn_dev = r.dyn_now; r.dyn_pending = false;
+    __atomic_thread_fence(__ATOMIC_RELEASE);
+    HIPCHK(hipGraphLaunch(ge, stream));
+    iter[Q_RAISE] += r.nr; iter[Q_LOWER] += r.nl;
+    last_active = 1;
+    return wait_published();
+}
+
+// Route::FusedChain / Separate: seeds -> invalidation bound -> a blind batch of invalidation launches -> re-lower what they touched ->
+// a blind batch of lowering launches -> device-side check -> finalise if the check says "done"; the control steps fused or one by one
+int Engine::submit_chain(StepRun &r) {
+    const bool fused = r.plan.fused;
+    flush_dyn(r);
+    if (fused) {
+        r.rb.k_raise = iter[Q_RAISE]; r.rb.band = r.band;
+        k_replan_begin<<<1, 1024, 0, stream>>>(P, r.rb);
+    } else {
+        k_seeds_to_active<<<1, 1024, 0, stream>>>(P, Q_RAISE, iter[Q_RAISE]);
+        k_prepare_bound<<<1, 64, 0, stream>>>(P, r.band);
+        k_unpark<<<1, 1024, 0, stream>>>(P, Q_RAISE, iter[Q_RAISE], -1.0f);
+    }
+    hipEvent_t *e = chain_ev;
+    if (profiling) {
+        for (auto &v : chain_ev) if (!v) HIPCHK(hipEventCreate(&v));
+        HIPCHK(hipEventRecord(e[0], stream));
+    }
+    last_active = 1;             // replans touch a handful of tiles: fused triage
+    for (int i = 0; i < r.nr; ++i) launch_relax(MODE_RAISE, -1.0f);
+    if (profiling) HIPCHK(hipEventRecord(e[1], stream));
+    if (fused) {
+        k_raise_to_lower<<<1, 1024, 0, stream>>>(P, iter[Q_LOWER]);
+    } else {
+        k_touched_to_active<<<64, 256, 0, stream>>>(P, Q_LOWER, iter[Q_LOWER]);
+        k_unpark<<<1, 1024, 0, stream>>>(P, Q_LOWER, iter[Q_LOWER], INFINITY);
+    }
+    if (profiling) HIPCHK(hipEventRecord(e[2], stream));
+    for (int i = 0; i < r.nl; ++i) launch_relax(MODE_LOWER, INFINITY);
+    if (profiling) HIPCHK(hipEventRecord(e[3], stream));
+    if (fused) {
+        int rc = fused_end(r.band);
+        if (rc != UFM_OK) return rc;
+    } else {
+        k_check<<<1, 1024, 0, stream>>>(P, iter[Q_RAISE], iter[Q_LOWER], r.band);
+        finalize_bp(1);
+        k_finalize<<<2048, 256, 0, stream>>>(P, 1);
+        HIPCHK(hipGetLastError());
+        int rc = fetch_counters();
+        if (rc != UFM_OK) return rc;
+    }
+    if (profiling) {
+        float ms = 0;
+        HIPCHK(hipEventElapsedTime(&ms, e[0], e[1])); r.st.kernel_ms += ms; r.st.raise_kernel_ms += ms;
+        HIPCHK(hipEventElapsedTime(&ms, e[2], e[3])); r.st.kernel_ms += ms;
+    }
+    return UFM_OK;
+}
+
+// A replan: one submission, one host round trip, by the route plan_step chose.  (An empty launch costs a few microseconds; a host
+// round trip costs more.)  If that was not enough, converge() takes over.
+int Engine::replan(StepRun &r) {
+    const Route route = r.plan.route;
+    const bool block = route == Route::BlockSingle || route == Route::BlockBatch;
+    const int k0_raise = iter[Q_RAISE], k0_lower = iter[Q_LOWER];
+    { int rc = block ? submit_block(r) : (route == Route::Graph ? submit_graph(r) : submit_chain(r)); if (rc != UFM_OK) return rc; }
+    r.updated += h_ctr->updated;
+    r.fast_done = h_ctr->done != 0;
+    ufm_stats &st = r.st;
+    if (block) {
+        st.launches += 1u;
+        return (!r.fast_done && spin_wait && cont_lower > 0) ? continue_block(r) : UFM_OK;
+    }
+    st.raise_launches += (uint32_t)r.nr;
+    st.launches += (uint32_t)(r.nr + r.nl);
+    // (launches replayed from the graph are not event-timed: HIP cannot read events recorded by graph nodes)
+    if (profiling && route != Route::Graph) { st.timed_launches += (uint32_t)(r.nr + r.nl); st.timed_raise_launches += (uint32_t)r.nr; }
+    // launches the batches actually needed (for the next steps' batch sizes); a batch that was
+    // too short costs a host round trip and the adaptive loop, so err on the long side after one
+    const int need_r = std::max(0, h_ctr->last_work[Q_RAISE] - k0_raise + 1);
+    const int need_l = std::max(0, h_ctr->last_work[Q_LOWER] - k0_lower + 1);
+    win_raise[win_pos] = r.fast_done ? need_r : r.nr + 2;
+    win_lower[win_pos] = r.fast_done ? need_l : r.nl + 2;
+    win_pos = (win_pos + 1) % 6;
+    return UFM_OK;
+}
+
+// Route::SeedsOnly: the seeds of initialising maps go to the queue, converge() plans
+int Engine::seed_only(StepRun &r) {
+    flush_dyn(r);
+    // num_nodes_updated (FD impl:138, DFM impl:109) of the participating maps
+    HIPCHK(hipMemcpyAsync(scratch.num_updated, P.num_updated, sizeof(unsigned int) * nmaps, hipMemcpyDeviceToHost, stream));
+    // patches enter an existing field through the invalidation queue, a fresh one directly
+    const int sq = (r.plan.n_upd > 0) ? Q_RAISE : Q_LOWER;
+    k_seeds_to_active<<<1, 1024, 0, stream>>>(P, sq, iter[sq]);
+    HIPCHK(hipStreamSynchronize(stream));
     for (int m = 0; m < nmaps; ++m) {
-        MapState &ms = maps[m];
-        if (ms.initialize_search || ms.new_goal)
-            HIPCHK(hipMemcpyAsync(P.goal + 2 * m, goals + 2 * m, 2 * sizeof(int), hipMemcpyHostToDevice, stream));
+        if (!scratch.consume[m]) continue;
+        if (!scratch.init[m]) r.updated += scratch.num_updated[m];
+        HIPCHK(hipMemsetAsync(P.num_updated + m, 0, sizeof(unsigned int), stream));
     }
-    // replan of a single map with a few small pending patches: the control steps run fused
-    // (k_replan_begin / k_raise_to_lower / k_replan_end) instead of as ten separate launches
-    ReplanBegin rb{};
-    bool fused = single && fuse_control && spin_wait && n_init == 0 && n_upd > 0 && !pending.empty() && pending.size() <= 4;
-    if (fused)
-        for (const PatchRect &r : pending) fused = fused && consume[r.m] && (r.w + 1) * (r.h + 1) <= 65 * 65;
-    {   // start elements: the 4 corners of the start cell (FD impl:9-13, Cell.cpp:48-60) / the start cell (DFM)
-        int *st_el = h_scratch + 5 * nmaps + 4;
-        float *sp = reinterpret_cast<float *>(h_scratch + 9 * nmaps + 8);
-        for (int m = 0; m < nmaps; ++m) {
-            const MapState &ms = maps[m];
-            for (int i = 0; i < 4; ++i) st_el[4 * m + i] = -1;
-            sp[2 * m] = sp[2 * m + 1] = 0.0f;
-            if (!ms.start_set) continue;
-            const int cx = (int)(start_cell_floor ? std::floor(ms.start_x) : std::roundf(ms.start_x)), cy = (int)(start_cell_floor ? std::floor(ms.start_y) : std::roundf(ms.start_y));
-            // keys measure from start_pos_ (FD/SG, Position::distance) or from start_cell_ (DFM, Cell::distance)
-            sp[2 * m] = (algo == UFM_ALGO_DFM) ? (float)cx : ms.start_x;
-            sp[2 * m + 1] = (algo == UFM_ALGO_DFM) ? (float)cy : ms.start_y;
-            const int ncorner = (algo == UFM_ALGO_DFM) ? 1 : 4;
-            for (int i = 0; i < ncorner; ++i) {
-                const int ex = cx + (i & 1), ey = cy + (i >> 1);
-                if (ex >= 0 && ey >= 0 && ex < P.EX && ey < P.EY) st_el[4 * m + i] = ex * P.EY + ey;
-            }
-        }
-        if (single) {
-            for (int i = 0; i < 4; ++i) rb.sb.start[i] = st_el[i];
-            rb.sb.consume = consume[0];
-            rb.sb.clear_lmax = profiling ? 1 : 0;
-            rb.sb.sx = sp[0]; rb.sb.sy = sp[1];
-            if (!fused) k_step_begin<<<1, 256, 0, stream>>>(P, rb.sb);
+    return UFM_OK;
+}
+
+// The adaptive rounds.  Invalidate, then lower, both only as far as the start's key (the reference's end_condition).  The
+// invalidation bound must reach the key the start ends up with, which is only known afterwards: start from the current key plus
+// one ordering band and repeat while invalidations below the new key are still queued.
+int Engine::converge(StepRun &r) {
+    const StepPlan &pl = r.plan;
+    ufm_stats &st = r.st;
+    const bool do_raise = pl.have_seeds && pl.n_upd > 0;
+    flush_dyn(r);
+    float rbound = INFINITY;
+    if (focused && do_raise) {
+        if (h_ctr->rbound > 0.0f && pl.n_init == 0 && pl.n_upd > 0) {
+            rbound = h_ctr->rbound;      // continue from the replan's (possibly enlarged) bound
         } else {
-            HIPCHK(hipMemcpyAsync(P.start, st_el, sizeof(int) * 4 * nmaps, hipMemcpyHostToDevice, stream));
-            HIPCHK(hipMemcpyAsync(P.spos, sp, sizeof(float) * 2 * nmaps, hipMemcpyHostToDevice, stream));
+            float b0 = 0.0f;
+            int rc = read_bounds(&b0);
+            if (rc != UFM_OK) return rc;
+            rbound = b0 + r.band;
         }
     }
-    uint64_t updated = 0;
-    bool have_seeds = false;
-    bool fast_done = false;
-    bool skip_raise = false;      // the block kernel has left nothing to invalidate below its bound (only lowering work beyond the block)
-    // margin of the invalidation bound above the start's current key (the key may rise through the patch)
-    const float band = raise_margin * (delta_abs >= 0.0f ? delta_abs : delta_scale * T * mean_cost);
-    if (n_upd > 0 || n_init > 0) {
-        if (!single) HIPCHK(hipMemcpyAsync(P.consume, consume, sizeof(int) * nmaps, hipMemcpyHostToDevice, stream));
-        // consume pending patch rectangles of the participating maps
-        std::vector<PatchRect> keep;
-        region_rects.clear();
-        for (const PatchRect &r : pending) {
-            if (!consume[r.m]) { keep.push_back(r); continue; }
-            have_seeds = true;
-            region_rects.push_back(r);
-            const int cnt = (r.h + 1) * (r.w + 1);
-            if (fused) { int *q = rb.rect[rb.nrect++]; q[0] = r.m; q[1] = r.x; q[2] = r.y; q[3] = r.w; q[4] = r.h; }
-            else k_clear_marks<<<(cnt + 255) / 256, 256, 0, stream>>>(P, r.m, r.x, r.y, r.w, r.h);
-        }
-        pending.swap(keep);
-    }
-    const auto t_seed = std::chrono::steady_clock::now();
-    if (have_seeds && n_init == 0 && n_upd > 0) {
-        // Replan fast path: one submission, one host round trip.  Seeds -> invalidation bound ->
-        // a blind batch of invalidation launches -> re-lower what they touched -> a blind batch of
-        // lowering launches -> device-side check -> finalise if the check says "done".  (An empty
-        // launch costs a few microseconds; a host round trip costs more.)  If the batches were too
-        // short the general adaptive loop below takes over.
-        // blind batch sizes: what the recent replans needed, plus one
-        int nr = 1, nl = 1;
-        for (int i = 0; i < 6; ++i) { nr = std::max(nr, win_raise[i] + batch_margin); nl = std::max(nl, win_lower[i] + batch_margin); }
-        const int k0_raise = iter[Q_RAISE], k0_lower = iter[Q_LOWER];
-        if (profiling) while (ev.size() < 4) { hipEvent_t a; HIPCHK(hipEventCreate(&a)); ev.push_back(a); }
-        // The block around the patches (ufm_region.h): its goal-side edge `region_ahead` tiles beyond the patches' centre,
-        // the rest of its extent behind it -- where the elements that lean on the patched cells are.
-        RegionJobs rjs{};
-        bool regioned = false;
-        {
-            // the block of one map: around its consumed rectangles; false if they do not fit into one block
-            auto place_job = [&](RegionJob &j, const ReplanBegin &b, int m) {
-                if (!region_fits(b.rect, b.nrect, m, &j.tx0, &j.ntx, &j.ty0, &j.nty)) return false;
-                j.rb = b; j.rb.k_raise = iter[Q_RAISE]; j.rb.band = band;
-                j.dyn = dyn_now; j.k_lower = iter[Q_LOWER]; j.max_sweeps = region_sweeps; j.debug = region_debug;
-                j.slack = 255.0f * SQRT2F + 1.0f;     // the largest cost of one move (a diagonal through the most expensive cell)
-                j.delta = region_band > 0.0f ? region_band * 4.0f * mean_cost : INFINITY;
-                j.map = m;
-                for (int r = 0; r < 4; ++r) j.psrc[r] = nullptr;
-                return true;
-            };
-            if (fused && use_region) {                       // one map, a few small patches
-                regioned = place_job(rjs.j[0], rb, 0);
-                rjs.n = 1; rjs.j[0].batch = 0;
-                if (lazy_in_kernel) {                        // the held host patches are the last rectangles: the kernel applies them
-                    if (!regioned || lazy.size() > (size_t)rb.nrect) return UFM_ERR_INVALID;      // (lazy_region_ok() said otherwise: cannot happen)
-                    for (size_t i = 0; i < lazy.size(); ++i) {
-                        rjs.j[0].psrc[rb.nrect - (int)lazy.size() + (int)i] = h_lazy + (size_t)lazy[i].slot * 4096;
-                    }       // (the kernel has read them when this step returns: the slots are free again then)
-                    lazy.clear();
-                }
-            } else if (!single && use_region && spin_wait && nmaps <= RJOBS && !region_rects.empty()) {
-                // a batch: one job per consuming map, every one of them with 1..4 small rectangles of its own
-                bool ok = true;
-                rjs.n = 0;
-                const int *st_el = h_scratch + 5 * nmaps + 4;
-                const float *sp = reinterpret_cast<const float *>(h_scratch + 9 * nmaps + 8);
-                for (int m = 0; m < nmaps && ok; ++m) {
-                    if (!consume[m]) continue;
-                    ReplanBegin b{};
-                    for (const PatchRect &r : region_rects) {
-                        if (r.m != m) continue;
-                        if (b.nrect >= 4 || (r.w + 1) * (r.h + 1) > 65 * 65) { ok = false; break; }
-                        int *q = b.rect[b.nrect++]; q[0] = r.m; q[1] = r.x; q[2] = r.y; q[3] = r.w; q[4] = r.h;
-                    }
-                    for (int i = 0; i < 4; ++i) b.sb.start[i] = st_el[4 * m + i];
-                    b.sb.consume = 1; b.sb.sx = sp[2 * m]; b.sb.sy = sp[2 * m + 1];
-                    RegionJob &j = rjs.j[rjs.n];
-                    ok = ok && place_job(j, b, m);
-                    j.batch = 1;
-                    ++rjs.n;
-                }
-                regioned = ok && rjs.n > 0;
-            }
-        }
-        const bool graphed = !regioned && fused && use_graph && nr < 250 && nl < 250;
-        if (regioned) {
-            const unsigned int seq = ++pub_seq;
-            for (int i = 0; i < rjs.n; ++i) rjs.j[i].seq = seq;
-            if (rjs.j[0].batch) {   // the counters the maps' workgroups add to
-                HIPCHK(hipMemsetAsync(&P.ctr->rbound, 0, offsetof(DevCounters, done_fail) + sizeof(int) - offsetof(DevCounters, rbound), stream));
-                k_fill<<<1, 64, 0, stream>>>(reinterpret_cast<float *>(&P.ctr->qmin[Q_RAISE]), (size_t)1, INFINITY);
-            }
-            // the per-step scalars: a single map's workgroup stores the job's copy itself (it is the only reader before the next launch); a batch's
-            // workgroups read *P.dyn side by side (start_bound, tile_heuristic), so there it is in place before the launch
-            if (rjs.j[0].batch) flush_dyn();
-            else { dyn_dev = dyn_now; dyn_pending = false; }
-            const dim3 g(rjs.n), b(NTHR);
-            const bool reg_timed = profiling && (region_runs & 7u) == 0u;     // a sample: the event packets cost a few microseconds each
-            if (reg_timed) for (auto &e : reg_ev) if (!e) HIPCHK(hipEventCreate(&e));
-#define UFM_LAUNCH(A) do { if (reg_timed) hipExtLaunchKernelGGL((k_replan_region<A>), g, b, 0, stream, reg_ev[0], reg_ev[1], 0, P, rjs, h_ctr, h_flag); \
-                           else k_replan_region<A><<<g, b, 0, stream>>>(P, rjs, h_ctr, h_flag); } while (0)
-            if (algo == UFM_ALGO_FD) UFM_LAUNCH(UFM_ALGO_FD);
-            else if (algo == UFM_ALGO_SG) UFM_LAUNCH(UFM_ALGO_SG);
-            else if (dfm_follow_info) UFM_LAUNCH(ALGO_DFM1_INFO);
-            else UFM_LAUNCH(ALGO_DFM1);
-#undef UFM_LAUNCH
-            HIPCHK(hipGetLastError());
-            last_active = 1;
-            int rc = wait_published();
+    for (int round = 0; round < 64; ++round) {
+        const auto ta = std::chrono::steady_clock::now();
+        if (do_raise && !(r.skip_raise && round == 0)) {
+            uint32_t rl = 0, rt = 0;
+            float rk = 0.0f;
+            k_unpark<<<1, 1024, 0, stream>>>(P, Q_RAISE, iter[Q_RAISE], rbound);
+            int rc = run_phase(MODE_RAISE, rbound, &rl, &rk, &rt);
             if (rc != UFM_OK) return rc;
-            st.region_launches = 1u;
-            for (int i = 0; i < rjs.n; ++i) st.region_tiles += (uint32_t)(rjs.j[i].ntx * rjs.j[i].nty);
-            if (reg_timed) {      // (the kernel has published its result: its stop event follows within microseconds -- spin, do not sleep)
-                hipError_t q;
-                while ((q = hipEventQuery(reg_ev[1])) == hipErrorNotReady) __builtin_ia32_pause();
-                HIPCHK(q);
-                HIPCHK(hipEventElapsedTime(&st.region_kernel_ms, reg_ev[0], reg_ev[1]));
-                st.region_timed = 1u;
-            }
-            region_runs += (uint32_t)rjs.n;
-            if (h_ctr->done) region_done += (uint32_t)rjs.n;
-            else if (focused) {
-                // (its end check has the smallest invalidation priority of the map -- of any map of a batch --, queued or parked: at or
-                //  beyond the bound -- a batch: the largest of the maps' bounds -- means the launch chain's invalidation phase, two batches
-                //  of launches and two host round trips, would release nothing)
-                float qm;
-                std::memcpy(&qm, &h_ctr->qmin[Q_RAISE], sizeof(float));
-                skip_raise = !(qm < h_ctr->rbound);
-            }
-        } else if (graphed) {
-            rb.k_raise = iter[Q_RAISE]; rb.band = band;
-            hipGraphExec_t ge = nullptr;
-            int rc = replan_graph(nr, nl, band, &ge);
-            if (rc != UFM_OK) return rc;
-            h_job->rb = rb; h_job->k_lower = iter[Q_LOWER]; h_job->seq = ++pub_seq;
-            h_job->dyn = dyn_now; dyn_dev = dyn_now; dyn_pending = false;
-            __atomic_thread_fence(__ATOMIC_RELEASE);
-            HIPCHK(hipGraphLaunch(ge, stream));
-            iter[Q_RAISE] += nr; iter[Q_LOWER] += nl;
-            last_active = 1;
-            rc = wait_published();
-            if (rc != UFM_OK) return rc;
-        } else {
-        flush_dyn();
-        if (fused) {
-            rb.k_raise = iter[Q_RAISE]; rb.band = band;
-            k_replan_begin<<<1, 1024, 0, stream>>>(P, rb);
-        } else {
-            k_seeds_to_active<<<1, 1024, 0, stream>>>(P, Q_RAISE, iter[Q_RAISE]);
-            k_prepare_bound<<<1, 64, 0, stream>>>(P, band);
-            k_unpark<<<1, 1024, 0, stream>>>(P, Q_RAISE, iter[Q_RAISE], -1.0f);
-        }
-        hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr, e3 = nullptr;
-        if (profiling) {
-            while (ev.size() < 4) { hipEvent_t a; HIPCHK(hipEventCreate(&a)); ev.push_back(a); }
-            e0 = ev[0]; e1 = ev[1]; e2 = ev[2]; e3 = ev[3];
-            HIPCHK(hipEventRecord(e0, stream));
-        }
-        last_active = 1;             // replans touch a handful of tiles: fused triage
-        for (int i = 0; i < nr; ++i) launch_relax(MODE_RAISE, -1.0f);
-        if (profiling) HIPCHK(hipEventRecord(e1, stream));
-        if (fused) {
-            k_raise_to_lower<<<1, 1024, 0, stream>>>(P, iter[Q_LOWER]);
-        } else {
+            st.kernel_ms += rk; st.raise_kernel_ms += rk;
+            st.timed_launches += rt; st.timed_raise_launches += rt;
+            st.raise_launches += rl;
+            st.launches += rl;
+            // everything invalidation touched must be re-lowered
             k_touched_to_active<<<64, 256, 0, stream>>>(P, Q_LOWER, iter[Q_LOWER]);
-            k_unpark<<<1, 1024, 0, stream>>>(P, Q_LOWER, iter[Q_LOWER], INFINITY);
         }
-        if (profiling) HIPCHK(hipEventRecord(e2, stream));
-        for (int i = 0; i < nl; ++i) launch_relax(MODE_LOWER, INFINITY);
-        if (profiling) HIPCHK(hipEventRecord(e3, stream));
-        if (fused) {
-            ++pub_seq;
-            k_replan_end<<<64, T * T, 0, stream>>>(P, iter[Q_RAISE], iter[Q_LOWER], band, h_ctr, h_flag, pub_seq);
-            finalize_bp(1);
-            HIPCHK(hipGetLastError());
-            int rc = wait_published();
+        const auto tb = std::chrono::steady_clock::now();
+        uint32_t ll = 0;
+        k_unpark<<<1, 1024, 0, stream>>>(P, Q_LOWER, iter[Q_LOWER], INFINITY);
+        int owned_left = -1;
+        if (use_owned && pl.n_init > 0 && round == 0 && dyn_grid >= 256) {
+            int rc = owned_phase();
             if (rc != UFM_OK) return rc;
-        } else {
-            k_check<<<1, 1024, 0, stream>>>(P, iter[Q_RAISE], iter[Q_LOWER], band);
-            finalize_bp(1);
-            k_finalize<<<2048, 256, 0, stream>>>(P, 1);
-            HIPCHK(hipGetLastError());
-            int rc = fetch_counters();
-            if (rc != UFM_OK) return rc;
-        }
-        if (profiling) {
-            float ms = 0;
-            HIPCHK(hipEventElapsedTime(&ms, e0, e1)); st.kernel_ms += ms; st.raise_kernel_ms += ms;
-            HIPCHK(hipEventElapsedTime(&ms, e2, e3)); st.kernel_ms += ms;
-        }
-        }   // !graphed
-        updated += h_ctr->updated;
-        fast_done = h_ctr->done != 0;
-        if (regioned) {
             st.launches += 1u;
-            if (!fast_done && spin_wait && cont_lower > 0) {
-                // The block kernel has left work beyond its block (3 of the headline's 100 replans; a round of a batch as soon as ONE of its maps
-                // has): the launch chain takes over from the queues -- first as ONE blind submission ending in the device-side end check, like
-                // the fused replan path (a few launches that may find nothing to do are cheaper than the adaptive loop's host round trips:
-                // that loop cost a batch round of config 4 ~0.6 ms), and only if that was not enough through the adaptive loop below.
-                // (one invalidation launch even when the block kernel saw nothing to invalidate below its bound: the end check reads what the
-                //  last launch of each phase released)
-                const int nr2 = skip_raise ? 1 : std::max(1, cont_raise), nl2 = cont_lower;
-                last_active = 1;
-                k_unpark<<<1, 1024, 0, stream>>>(P, Q_RAISE, iter[Q_RAISE], -1.0f);       // (-1: the bound the block kernel left in the counters)
-                for (int i = 0; i < nr2; ++i) launch_relax(MODE_RAISE, -1.0f);
-                k_raise_to_lower<<<1, 1024, 0, stream>>>(P, iter[Q_LOWER]);
-                for (int i = 0; i < nl2; ++i) launch_relax(MODE_LOWER, INFINITY);
-                ++pub_seq;
-                k_replan_end<<<64, T * T, 0, stream>>>(P, iter[Q_RAISE], iter[Q_LOWER], band, h_ctr, h_flag, pub_seq);
-                finalize_bp(1);
-                HIPCHK(hipGetLastError());
-                int rc = wait_published();
-                if (rc != UFM_OK) return rc;
-                fast_done = h_ctr->done != 0;
-                st.raise_launches += (uint32_t)nr2;
-                st.launches += (uint32_t)(nr2 + nl2);
-                skip_raise = false;
-                ++region_cont; if (fast_done) ++region_cont_done;
-            }
-        } else {
-        st.raise_launches += (uint32_t)nr;
-        st.launches += (uint32_t)(nr + nl);
-        // (launches replayed from the graph are not event-timed: HIP cannot read events recorded by graph nodes)
-        if (profiling && !graphed) { st.timed_launches += (uint32_t)(nr + nl); st.timed_raise_launches += (uint32_t)nr; }
-        // launches the batches actually needed (for the next steps' batch sizes); a batch that was
-        // too short costs a host round trip and the adaptive loop, so err on the long side after one
-        {
-            const int need_r = std::max(0, h_ctr->last_work[Q_RAISE] - k0_raise + 1);
-            const int need_l = std::max(0, h_ctr->last_work[Q_LOWER] - k0_lower + 1);
-            win_raise[win_pos] = fast_done ? need_r : nr + 2;
-            win_lower[win_pos] = fast_done ? need_l : nl + 2;
-            win_pos = (win_pos + 1) % 6;
+            st.resident_launches += 1u;
+            // what it handed back (nothing, unless it ran into its time limit): no need to send launches after an empty list
+            rc = fetch_counters();
+            if (rc != UFM_OK) return rc;
+            owned_left = h_ctr->cnt[Q_LOWER][iter[Q_LOWER] % 3];
         }
+        int rc = owned_left == 0 ? UFM_OK : run_phase(MODE_LOWER, INFINITY, &ll, &st.kernel_ms, &st.timed_launches);
+        if (rc != UFM_OK) return rc;
+        st.launches += ll;
+        bool again = false;
+        if (focused && do_raise) {
+            float bnew = 0.0f;
+            rc = read_bounds(&bnew);
+            if (rc != UFM_OK) return rc;
+            k_queue_min<<<1, 1024, 0, stream>>>(P, Q_RAISE, iter[Q_RAISE]);
+            rc = fetch_counters();
+            if (rc != UFM_OK) return rc;
+            float qm;
+            std::memcpy(&qm, &h_ctr->qmin[Q_RAISE], sizeof(float));
+            if (qm < bnew) { again = true; rbound = std::fmax(bnew, rbound) + r.band; }
         }
-    } else if (have_seeds) {
-        flush_dyn();
-        // num_nodes_updated (FD impl:138, DFM impl:109) of the participating maps
-        HIPCHK(hipMemcpyAsync(h_scratch + 2 * nmaps + 2 * nmaps, P.num_updated, sizeof(unsigned int) * nmaps, hipMemcpyDeviceToHost, stream));
-        // patches enter an existing field through the invalidation queue, a fresh one directly
-        const int sq = (n_upd > 0) ? Q_RAISE : Q_LOWER;
-        k_seeds_to_active<<<1, 1024, 0, stream>>>(P, sq, iter[sq]);
-        HIPCHK(hipStreamSynchronize(stream));
-        const unsigned int *nu = reinterpret_cast<const unsigned int *>(h_scratch + 4 * nmaps);
-        for (int m = 0; m < nmaps; ++m) {
-            MapState &ms = maps[m];
-            if (!consume[m]) continue;
-            if (!(ms.initialize_search || ms.new_goal)) updated += nu[m];
-            HIPCHK(hipMemsetAsync(P.num_updated + m, 0, sizeof(unsigned int), stream));
-        }
+        const auto tc = std::chrono::steady_clock::now();
+        r.u_acc += std::chrono::duration<double, std::milli>(tb - ta).count();
+        r.p_acc += std::chrono::duration<double, std::milli>(tc - tb).count();
+        if (!again) break;
     }
-    if (n_init > 0) {
-        int k = 0;
-        for (int m = 0; m < nmaps; ++m) {
-            MapState &ms = maps[m];
-            if ((ms.initialize_search || ms.new_goal) && ms.goal_elem_valid) ++k;
-        }
-        if (k > 0) {
-            HIPCHK(hipMemcpyAsync(d_scratch, init_tiles, sizeof(int) * k, hipMemcpyHostToDevice, stream));
-            k_activate_list<<<1, 64, 0, stream>>>(P, Q_LOWER, iter[Q_LOWER], d_scratch, k);
-        }
+    const auto td = std::chrono::steady_clock::now();
+    finalize_bp(0);
+    k_finalize<<<2048, 256, 0, stream>>>(P, 0);
+    { int rc = fetch_counters(); if (rc != UFM_OK) return rc; }
+    copy_counters(st);
+    if (st.resident_launches) {
+        st.resident_tile_visits = h_ctr->own_vis1 - h_ctr->own_vis0;
+        st.resident_stops = (uint32_t)h_ctr->own_stops;
+        if (own_timed) HIPCHK(hipEventElapsedTime(&st.resident_kernel_ms, own_ev[0], own_ev[1]));
+    }
+    if (profiling) {   // diagnostics: sum over launches of the slowest tile's sweep count
+        std::vector<int> lm(LMAX);
+        HIPCHK(hipMemcpy(lm.data(), P.lmax, sizeof(int) * LMAX, hipMemcpyDeviceToHost));
+        for (int v : lm) st.crit_sweeps += (uint64_t)v;
+    }
+    r.p_acc += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - td).count();
+    return UFM_OK;
+}
+
+void Engine::copy_counters(ufm_stats &st) const {   // the published counter block into the step's statistics
+    st.expanded = h_ctr->expanded;
+    st.tile_visits = h_ctr->tile_visits;
+    st.tile_iters = h_ctr->tile_iters;
+    st.elem_evals = h_ctr->elem_evals;
+    st.raise_tile_visits = h_ctr->raise_visits;
+}
+
+int Engine::step(ufm_stats *out) {
+    // ReplannerBase.h:44-45
+    for (int m = 0; m < nmaps; ++m) if (!maps[m].have_map) return UFM_LOOP_FAILURE_NO_GRAPH;
+    for (int m = 0; m < nmaps; ++m) if (!maps[m].goal_set) return UFM_LOOP_FAILURE_NO_GOAL;
+    StepRun r{};
+    r.t0 = std::chrono::steady_clock::now();
+    // blind batch sizes of a replan: what the recent replans needed, plus one
+    r.nr = r.nl = 1;
+    for (int i = 0; i < 6; ++i) { r.nr = std::max(r.nr, win_raise[i] + batch_margin); r.nl = std::max(r.nl, win_lower[i] + batch_margin); }
+    r.plan = plan_step(ROUTE_CONFIG, route_switches(), maps.data(), pending.data(), (int)pending.size(), (int)lazy.size(), r.nr, r.nl,
+                       scratch.consume, scratch.init);
+    const StepPlan &pl = r.plan;
+    r.dyn_now = DevDyn{heur ? heuristic_multiplier : 0.0f, thr_uchar, focused ? 1 : 0, 0};
+    r.dyn_pending = std::memcmp(&r.dyn_now, &dyn_dev, sizeof(DevDyn)) != 0;
+    r.band = raise_margin * band_delta(delta_scale);
+    { int rc = begin_step(r); if (rc != UFM_OK) return rc; }
+    r.t_seed = std::chrono::steady_clock::now();
+    if (pl.route == Route::SeedsOnly) { int rc = seed_only(r); if (rc != UFM_OK) return rc; }
+    else if (pl.route != Route::None) { int rc = replan(r); if (rc != UFM_OK) return rc; }
+    if (r.n_init_tiles > 0) {        // the goal tiles of the initialising maps: where their plans start
+        HIPCHK(hipMemcpyAsync(d_scratch, scratch.init_tiles, sizeof(int) * r.n_init_tiles, hipMemcpyHostToDevice, stream));
+        k_activate_list<<<1, 64, 0, stream>>>(P, Q_LOWER, iter[Q_LOWER], d_scratch, r.n_init_tiles);
     }
     // ReplannerBase.h:65-69: plan() only if something was (re)initialised or updated
-    const bool do_plan = (n_init > 0 || updated > 0 || (have_seeds && n_upd > 0)) && !fast_done;
-    const bool do_raise = have_seeds && n_upd > 0;
-    auto t1 = std::chrono::steady_clock::now();
-    double u_acc = std::chrono::duration<double, std::milli>(t1 - t0).count(), p_acc = 0.0;
+    const bool do_plan = (pl.n_init > 0 || r.updated > 0 || (pl.have_seeds && pl.n_upd > 0)) && !r.fast_done;
+    r.u_acc = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - r.t0).count();
     if (do_plan) {
-        flush_dyn();
-        // Invalidate, then lower, both only as far as the start's key (the reference's
-        // end_condition).  The invalidation bound must reach the key the start ends up with, which
-        // is only known afterwards: start from the current key plus one ordering band and repeat
-        // while invalidations below the new key are still queued.
-        float rbound = INFINITY;
-        if (focused && do_raise) {
-            if (h_ctr->rbound > 0.0f && n_init == 0 && n_upd > 0) {
-                rbound = h_ctr->rbound;      // continue from the fast path's (possibly enlarged) bound
-            } else {
-                float b0 = 0.0f;
-                int rc = read_bounds(&b0);
-                if (rc != UFM_OK) return rc;
-                rbound = b0 + band;
-            }
-        }
-        for (int round = 0; round < 64; ++round) {
-            const auto ta = std::chrono::steady_clock::now();
-            if (do_raise && !(skip_raise && round == 0)) {
-                uint32_t rl = 0;
-                float rk = 0.0f;
-                k_unpark<<<1, 1024, 0, stream>>>(P, Q_RAISE, iter[Q_RAISE], rbound);
-                uint32_t rt = 0;
-                int rc = run_phase(MODE_RAISE, rbound, &rl, &rk, &rt);
-                if (rc != UFM_OK) return rc;
-                st.kernel_ms += rk; st.raise_kernel_ms += rk;
-                st.timed_launches += rt; st.timed_raise_launches += rt;
-                st.raise_launches += rl;
-                st.launches += rl;
-                // everything invalidation touched must be re-lowered
-                k_touched_to_active<<<64, 256, 0, stream>>>(P, Q_LOWER, iter[Q_LOWER]);
-            }
-            const auto tb = std::chrono::steady_clock::now();
-            uint32_t ll = 0;
-            k_unpark<<<1, 1024, 0, stream>>>(P, Q_LOWER, iter[Q_LOWER], INFINITY);
-            int owned_left = -1;
-            if (use_owned && n_init > 0 && round == 0 && dyn_grid >= 256) {
-                int rc = owned_phase();
-                if (rc != UFM_OK) return rc;
-                st.launches += 1u;
-                st.resident_launches += 1u;
-                // what it handed back (nothing, unless it ran into its time limit): no need to send launches after an empty list
-                rc = fetch_counters();
-                if (rc != UFM_OK) return rc;
-                owned_left = h_ctr->cnt[Q_LOWER][iter[Q_LOWER] % 3];
-            }
-            int rc = owned_left == 0 ? UFM_OK : run_phase(MODE_LOWER, INFINITY, &ll, &st.kernel_ms, &st.timed_launches);
-            if (rc != UFM_OK) return rc;
-            st.launches += ll;
-            bool again = false;
-            if (focused && do_raise) {
-                float bnew = 0.0f;
-                rc = read_bounds(&bnew);
-                if (rc != UFM_OK) return rc;
-                k_queue_min<<<1, 1024, 0, stream>>>(P, Q_RAISE, iter[Q_RAISE]);
-                rc = fetch_counters();
-                if (rc != UFM_OK) return rc;
-                float qm;
-                std::memcpy(&qm, &h_ctr->qmin[Q_RAISE], sizeof(float));
-                if (qm < bnew) { again = true; rbound = std::fmax(bnew, rbound) + band; }
-            }
-            const auto tc = std::chrono::steady_clock::now();
-            u_acc += std::chrono::duration<double, std::milli>(tb - ta).count();
-            p_acc += std::chrono::duration<double, std::milli>(tc - tb).count();
-            if (!again) break;
-        }
-        const auto td = std::chrono::steady_clock::now();
-        finalize_bp(0);
-        k_finalize<<<2048, 256, 0, stream>>>(P, 0);
-        { int rc = fetch_counters(); if (rc != UFM_OK) return rc; }
-        st.expanded = h_ctr->expanded;
-        st.tile_visits = h_ctr->tile_visits;
-        st.tile_iters = h_ctr->tile_iters;
-        st.elem_evals = h_ctr->elem_evals;
-        st.raise_tile_visits = h_ctr->raise_visits;
-        if (st.resident_launches) {
-            st.resident_tile_visits = h_ctr->own_vis1 - h_ctr->own_vis0;
-            st.resident_stops = (uint32_t)h_ctr->own_stops;
-            if (own_timed) HIPCHK(hipEventElapsedTime(&st.resident_kernel_ms, own_ev[0], own_ev[1]));
-        }
-        if (profiling) {   // diagnostics: sum over launches of the slowest tile's sweep count
-            std::vector<int> lm(LMAX);
-            HIPCHK(hipMemcpy(lm.data(), P.lmax, sizeof(int) * LMAX, hipMemcpyDeviceToHost));
-            for (int v : lm) st.crit_sweeps += (uint64_t)v;
-        }
-        p_acc += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - td).count();
-    } else if (fast_done) {
-        st.expanded = h_ctr->expanded;
-        st.tile_visits = h_ctr->tile_visits;
-        st.tile_iters = h_ctr->tile_iters;
-        st.elem_evals = h_ctr->elem_evals;
-        st.raise_tile_visits = h_ctr->raise_visits;
-        const double dt = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_seed).count();
-        u_acc += 0.5 * dt;   // invalidation and lowering ran in one submission: split evenly
-        p_acc += 0.5 * dt;
+        int rc = converge(r);
+        if (rc != UFM_OK) return rc;
+    } else if (r.fast_done) {
+        copy_counters(r.st);
+        const double dt = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - r.t_seed).count();
+        r.u_acc += 0.5 * dt;   // invalidation and lowering ran in one submission: split evenly
+        r.p_acc += 0.5 * dt;
     } else {
         HIPCHK(hipStreamSynchronize(stream));
     }
     for (int m = 0; m < nmaps; ++m) maps[m].new_goal = maps[m].initialize_search = false;
-    st.updated = updated;
+    ufm_stats &st = r.st;
+    st.updated = r.updated;
     st.queued_lower = (uint32_t)(h_ctr->cnt[Q_LOWER][iter[Q_LOWER] % 3] + h_ctr->npark[Q_LOWER]);   // parked beyond the start's key
     st.queued_raise = (uint32_t)(h_ctr->cnt[Q_RAISE][iter[Q_RAISE] % 3] + h_ctr->npark[Q_RAISE]);
     st.graphs_instantiated = graphs_made;
     st.region_replans = region_runs; st.region_replans_done = region_done;
-    st.u_ms = (float)u_acc;   // seeding + invalidation (the reference's update())
-    st.p_ms = (float)p_acc;   // propagation + finalisation (the reference's plan())
+    st.u_ms = (float)r.u_acc;   // seeding + invalidation (the reference's update())
+    st.p_ms = (float)r.p_acc;   // propagation + finalisation (the reference's plan())
     last = st;
     if (out) *out = st;
     return UFM_OK;
@@ -1284,7 +1224,7 @@ int engine_create(Engine **out, int n_maps, int algo, int opt_lvl, int use_heuri
         }
         (void)hipGetLastError();
     }
-    HIPCHK(hipHostMalloc(&e->h_scratch, sizeof(int) * (11 * n_maps + 16)));
+    { int rc = e->scratch.carve(n_maps); if (rc != UFM_OK) return rc; }
     HIPCHK(hipHostMalloc(&e->h_bnd, sizeof(float) * n_maps));
     *out = e;
     return UFM_OK;
@@ -1295,26 +1235,15 @@ int engine_destroy(Engine *e) {
     hipSetDevice(e->device);
     if (e->stream) hipStreamSynchronize(e->stream);
     e->release();
-    for (hipEvent_t v : e->ev) hipEventDestroy(v);
+    for (hipEvent_t v : e->batch_ev) hipEventDestroy(v);
+    for (hipEvent_t v : e->chain_ev) if (v) hipEventDestroy(v);
     for (hipEvent_t v : e->own_ev) if (v) hipEventDestroy(v);
     for (hipEvent_t v : e->reg_ev) if (v) hipEventDestroy(v);
     for (hipEvent_t v : e->trk_ev) if (v) hipEventDestroy(v);
-    if (e->d_patch) hipFree(e->d_patch);
-    if (e->d_pmask) hipFree(e->d_pmask);
-    if (e->d_field) hipFree(e->d_field);
-    if (e->d_info) hipFree(e->d_info);
-    if (e->d_jobs) hipFree(e->d_jobs);
-    if (e->h_jobs) hipHostFree(e->h_jobs);
-    if (e->d_path) hipFree(e->d_path);
-    if (e->h_path) hipHostFree(e->h_path);
-    if (e->h_patch) hipHostFree(e->h_patch);
-    if (e->h_lazy) hipHostFree(e->h_lazy);
+    free_all(hipFree, e->d_patch, e->d_pmask, e->d_field, e->d_info, e->d_jobs, e->d_path);
+    free_all(hipHostFree, e->h_jobs, e->h_path, e->h_patch, e->h_lazy);
     e->drop_graphs();
-    if (e->h_ctr) hipHostFree(e->h_ctr);
-    for (int i = 0; i < 2; ++i) if (e->h_pipe_ctr[i]) hipHostFree(e->h_pipe_ctr[i]);
-    if (e->h_job) hipHostFree(e->h_job);
-    if (e->h_scratch) hipHostFree(e->h_scratch);
-    if (e->h_bnd) hipHostFree(e->h_bnd);
+    free_all(hipHostFree, e->h_ctr, e->h_pipe_ctr[0], e->h_pipe_ctr[1], e->h_job, e->scratch.acc, e->h_bnd);
     if (e->stream) hipStreamDestroy(e->stream);
     delete e;
     return UFM_OK;
@@ -1338,7 +1267,7 @@ int engine_set_map(Engine *e, int m, const uint8_t *src, bool on_device, int wid
         unsigned long long *d_acc = reinterpret_cast<unsigned long long *>(e->d_scratch);
         HIPCHK(hipMemsetAsync(d_acc, 0, 2 * sizeof(unsigned long long), e->stream));
         k_cost_stats<<<512, 256, 0, e->stream>>>(e->P.cost + (size_t)m * e->P.cstride, (size_t)width * length, e->thr_uchar, d_acc);
-        unsigned long long *h_acc = reinterpret_cast<unsigned long long *>(e->h_scratch);
+        unsigned long long *h_acc = e->scratch.acc;
         HIPCHK(hipMemcpyAsync(h_acc, d_acc, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
         HIPCHK(hipStreamSynchronize(e->stream));
         if (h_acc[1] > 0) e->mean_cost = (float)((double)h_acc[0] / (double)h_acc[1]);
@@ -1363,14 +1292,8 @@ int engine_patch(Engine *e, int m, const uint8_t *src, bool on_device, int x, in
     }
     const size_t n = (size_t)w * h;
     if (n > e->d_patch_cap) {
-        if (e->d_patch || e->h_patch) HIPCHK(hipStreamSynchronize(e->stream));
-        if (e->d_patch) hipFree(e->d_patch);
-        if (e->h_patch) hipHostFree(e->h_patch);
-        e->d_patch = nullptr; e->h_patch = nullptr; e->d_patch_cap = 0;   // nothing dangling if an allocation below fails
         const size_t cap = n < 4096 ? 4096 : n;
-        HIPCHK(hipMalloc(&e->d_patch, cap));
-        HIPCHK(hipHostMalloc(&e->h_patch, cap));
-        e->d_patch_cap = cap;
+        { int rc = regrow(e->stream, cap, e->d_patch_cap, cap, e->d_patch, &e->h_patch); if (rc != UFM_OK) return rc; }
     } else {
         HIPCHK(hipStreamSynchronize(e->stream));   // staging buffers are reused
     }
@@ -1400,9 +1323,7 @@ int engine_read_field(Engine *e, int m, int x0, int y0, int nx, int ny, float *g
     // the field is tile-major on the device: gather the window into a dense buffer, then one copy
     const size_t n = (size_t)nx * ny;
     if (n > e->d_field_cap) {
-        if (e->d_field) { HIPCHK(hipStreamSynchronize(e->stream)); hipFree(e->d_field); e->d_field = nullptr; e->d_field_cap = 0; }
-        HIPCHK(hipMalloc(&e->d_field, n * sizeof(float)));
-        e->d_field_cap = n;
+        { int rc = regrow(e->stream, n * sizeof(float), e->d_field_cap, n, e->d_field); if (rc != UFM_OK) return rc; }
     }
     k_gather_field<<<(unsigned)std::min<size_t>((n + 255) / 256, 65535), 256, 0, e->stream>>>(e->P, m, x0, y0, nx, ny, e->d_field);
     HIPCHK(hipGetLastError());
@@ -1419,6 +1340,14 @@ int engine_read_field(Engine *e, int m, int x0, int y0, int nx, int ny, float *g
 // held are applied first (the walk reads the raster).  Launches of at most PATH_CHUNK_JOBS walks, and of at most PATH_CHUNK_FLOATS of
 // output, so that the device and the pinned buffer stay bounded whatever n and max_steps are.
 struct PathQuery { int m; float sx, sy; size_t slot; };
+// map m's field and raster as the kernels of ufm_path.h and ufm_delta.h read them (FD: all five cost cases; SG: B / II / A)
+static PathField path_field(const Engine *e, int m) {
+    PathField F{};
+    F.G = e->P.G + (size_t)m * e->P.gstride; F.cost = e->P.cost + (size_t)m * e->P.cstride;
+    F.EX = e->P.EX; F.EY = e->P.EY; F.L = e->P.L; F.W = e->P.W; F.TY = e->P.TY; F.thr = e->thr_uchar;
+    F.cells = (e->algo == UFM_ALGO_DFM); F.indirect = (e->algo == UFM_ALGO_FD);
+    return F;
+}
 constexpr size_t PATH_CHUNK_JOBS = 65536, PATH_CHUNK_FLOATS = (size_t)16 << 20;
 
 int engine_walk(Engine *e, const PathQuery *q, size_t n, int max_steps, int lookahead, int allow_indirect,
@@ -1430,27 +1359,13 @@ int engine_walk(Engine *e, const PathQuery *q, size_t n, int max_steps, int look
     const size_t ostride = PATH_HDR + 2 * (size_t)dev_pts + dev_cst;
     const size_t chunk = std::min(n, std::min(PATH_CHUNK_JOBS, std::max<size_t>(PATH_CHUNK_FLOATS / ostride, 1)));
     if (ostride * chunk > e->path_cap) {
-        HIPCHK(hipStreamSynchronize(e->stream));
-        if (e->d_path) hipFree(e->d_path);
-        if (e->h_path) hipHostFree(e->h_path);
-        e->d_path = nullptr; e->h_path = nullptr; e->path_cap = 0;
-        HIPCHK(hipMalloc(&e->d_path, ostride * chunk * sizeof(float)));
-        HIPCHK(hipHostMalloc(&e->h_path, ostride * chunk * sizeof(float)));
-        e->path_cap = ostride * chunk;
+        { int rc = regrow(e->stream, ostride * chunk * sizeof(float), e->path_cap, ostride * chunk, e->d_path, &e->h_path, true); if (rc != UFM_OK) return rc; }
     }
     if (chunk > e->jobs_cap) {
-        HIPCHK(hipStreamSynchronize(e->stream));
-        if (e->d_jobs) hipFree(e->d_jobs);
-        if (e->h_jobs) hipHostFree(e->h_jobs);
-        e->d_jobs = nullptr; e->h_jobs = nullptr; e->jobs_cap = 0;
-        HIPCHK(hipMalloc(&e->d_jobs, sizeof(PathJob) * chunk));
-        HIPCHK(hipHostMalloc(&e->h_jobs, sizeof(PathJob) * chunk));
-        e->jobs_cap = chunk;
+        { int rc = regrow(e->stream, sizeof(PathJob) * chunk, e->jobs_cap, chunk, e->d_jobs, &e->h_jobs, true); if (rc != UFM_OK) return rc; }
     }
-    PathField F{};
-    F.G = e->P.G; F.cost = e->P.cost;
-    F.EX = e->P.EX; F.EY = e->P.EY; F.L = e->P.L; F.W = e->P.W; F.TY = e->P.TY; F.thr = e->thr_uchar;
-    F.cells = (e->algo == UFM_ALGO_DFM); F.indirect = allow_indirect != 0;
+    PathField F = path_field(e, 0);     // (the walks' jobs name their maps)
+    F.indirect = allow_indirect != 0;
     for (size_t first = 0; first < n; first += chunk) {
         const size_t cnt = std::min(chunk, n - first);
         for (size_t k = 0; k < cnt; ++k) {      // (the pinned buffers are free again: every chunk ends with a wait for the stream)
@@ -1538,17 +1453,12 @@ int engine_read_queue(Engine *e, int m, int cap, int32_t *xy, float *g_rhs, int 
     { int rc = e->flush_deferred(); if (rc != UFM_OK) return rc; }   // (the derived RHS / the stored bytes' view read the raster)
     const size_t words = (size_t)std::max(cap, 1) * 4 + 1;          // [cap][2] int32, [cap][2] float, the count
     if (words > e->d_info_cap) {
-        if (e->d_info) { HIPCHK(hipStreamSynchronize(e->stream)); hipFree(e->d_info); e->d_info = nullptr; e->d_info_cap = 0; }
-        HIPCHK(hipMalloc(&e->d_info, words * sizeof(int32_t)));
-        e->d_info_cap = words;
+        { int rc = regrow(e->stream, words * sizeof(int32_t), e->d_info_cap, words, e->d_info); if (rc != UFM_OK) return rc; }
     }
     int32_t *d_xy = e->d_info;
     float *d_gr = reinterpret_cast<float *>(e->d_info + (size_t)std::max(cap, 1) * 2);
     unsigned int *d_cnt = reinterpret_cast<unsigned int *>(e->d_info + (size_t)std::max(cap, 1) * 4);
-    PathField F{};
-    F.G = e->P.G + (size_t)m * e->P.gstride; F.cost = e->P.cost + (size_t)m * e->P.cstride;
-    F.EX = e->P.EX; F.EY = e->P.EY; F.L = e->P.L; F.W = e->P.W; F.TY = e->P.TY; F.thr = e->thr_uchar;
-    F.cells = (e->algo == UFM_ALGO_DFM); F.indirect = (e->algo == UFM_ALGO_FD);
+    const PathField F = path_field(e, m);
     const MapState &ms = e->maps[m];
     HIPCHK(hipMemsetAsync(d_cnt, 0, sizeof(unsigned int), e->stream));
     const size_t n = (size_t)e->P.EX * e->P.EY;
@@ -1578,15 +1488,10 @@ int engine_read_info(Engine *e, int m, int x0, int y0, int nx, int ny, int32_t *
     { int rc = e->flush_deferred(); if (rc != UFM_OK) return rc; }   // (the derived RHS / the stored bytes' view read the raster)
     const size_t n = (size_t)nx * ny;
     if (n * 2 > e->d_info_cap) {        // device buffer kept between calls (a consumer asks window after window)
-        if (e->d_info) { HIPCHK(hipStreamSynchronize(e->stream)); hipFree(e->d_info); e->d_info = nullptr; e->d_info_cap = 0; }
-        HIPCHK(hipMalloc(&e->d_info, n * 2 * sizeof(int32_t)));
-        e->d_info_cap = n * 2;
+        { int rc = regrow(e->stream, n * 2 * sizeof(int32_t), e->d_info_cap, n * 2, e->d_info); if (rc != UFM_OK) return rc; }
     }
     int32_t *d_out = e->d_info;
-    PathField F{};
-    F.G = e->P.G + (size_t)m * e->P.gstride; F.cost = e->P.cost + (size_t)m * e->P.cstride;
-    F.EX = e->P.EX; F.EY = e->P.EY; F.L = e->P.L; F.W = e->P.W; F.TY = e->P.TY; F.thr = e->thr_uchar;
-    F.cells = (e->algo == UFM_ALGO_DFM); F.indirect = (e->algo == UFM_ALGO_FD);   // FD: all five cost cases; SG: B / II / A
+    const PathField F = path_field(e, m);
     if (derived) k_info<<<(unsigned)((n + 255) / 256), 256, 0, e->stream>>>(F, e->opt_lvl, x0, y0, nx, ny, d_out);
     else k_info_stored<<<(unsigned)((n + 255) / 256), 256, 0, e->stream>>>(F, e->P.bp + (size_t)m * e->P.gstride, x0, y0, nx, ny, d_out);
     hipError_t err = hipGetLastError();
