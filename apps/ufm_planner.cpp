@@ -12,10 +12,13 @@
 // LinearInterpolationPathExtractor, reset / set_* / patch_map / step / extract_path, u_time,
 // p_time, e_time, map.size(), map.buckets.
 //
-//   ufm_planner [--planner FD|SG|DFM] [--level K] [--max-moves N] [--verify-follow] <fifo_in> <fifo_out>
+//   ufm_planner [--planner FD|SG|DFM] [--level K] [--max-moves N] [--verify-follow] [--inflate D] <fifo_in> <fifo_out>
 //        start, goal and the `tof` flag arrive in-band after the map (DFM/main.cpp:62-67)
 //   ufm_planner [...] <mapfile> <from_x> <from_y> <to_x> <to_y> <cspace> <fifo_in> <fifo_out> <gui> <tof> <outpath>
 //        the 11-argument form of FDSTAR/main.cpp:16-31 and SGDFM/main.cpp
+// --inflate D: the map and the patches on the wire are RAW and the engine plans on their dilation by the disc of diameter D
+// (ufm_set_cspace; x^2 + y^2 <= (D / 2)^2 on a (2 (D / 2) + 1)-cell square, the footprint of the Python harness' dilate) -- the simulator
+// then need not inflate anything.  The positional <cspace> stays as inert as it is in the reference drivers.
 // With `tof` the expanded-element dump after every step is kept up to date from the steps' deltas (ExpandedMap::follow_changes), not
 // read back whole; --verify-follow also builds it the old way every step -- a read of the whole field through a second view of the
 // same planner -- and ends the run (exit code 3) if the two differ in any element, value, Info or order.
@@ -72,6 +75,7 @@ struct Options {
   float from_x = 0, from_y = 0, to_x = 0, to_y = 0;
   bool tof = false;
   bool verify_follow = false;
+  int inflate = 0;           // --inflate D: footprint diameter (<= 1: off)
   std::string fifo_in, fifo_out;
 };
 
@@ -106,6 +110,15 @@ int serve(Options opt, bool cell_planner, bool indirect) {
   planner.reset();
   planner.set_occupancy_threshold(1);
   planner.set_heuristic_multiplier((float)min_cost);
+  if (opt.inflate > 1) {
+    const int r = opt.inflate / 2, n = 2 * r + 1;
+    if (n > 31) throw std::runtime_error("--inflate: the footprint is at most 31 cells wide");
+    std::vector<uint8_t> disc((size_t)n * n);
+    for (int a = 0; a < n; ++a)
+      for (int b = 0; b < n; ++b)
+        disc[(size_t)a * n + b] = (double)((b - r) * (b - r)) / (double)(r * r) + (double)((a - r) * (a - r)) / (double)(r * r) <= 1.0;
+    planner.set_cspace(disc.data(), n, n);
+  }
   planner.set_map(data, width, height);
   // the dump after every step: follow the steps' deltas on the host instead of reading the whole field back each time
   if (opt.tof && planner.map.follow_changes(true) != UFM_OK) throw std::runtime_error("follow_changes failed");
@@ -185,7 +198,7 @@ int serve(Options opt, bool cell_planner, bool indirect) {
 
 void usage(const char *argv0) {
   std::fprintf(stderr,
-               "Usage:\n\t%s [--planner FD|SG|DFM] [--level K] [--max-moves N] [--verify-follow] <fifo_in> <fifo_out>\n"
+               "Usage:\n\t%s [--planner FD|SG|DFM] [--level K] [--max-moves N] [--verify-follow] [--inflate D] <fifo_in> <fifo_out>\n"
                "\t%s [...] <mapfile> <from_x> <from_y> <to_x> <to_y> <cspace> <fifo_in> <fifo_out> <gui> <tof> <outpath>\n",
                argv0, argv0);
 }
@@ -215,6 +228,7 @@ int main(int argc, char **argv) {
     else if (a == "--level" && i + 1 < argc) opt.level = std::atoi(argv[++i]);
     else if (a == "--max-moves" && i + 1 < argc) opt.max_moves = std::atol(argv[++i]);
     else if (a == "--verify-follow") opt.verify_follow = true;
+    else if (a == "--inflate" && i + 1 < argc) opt.inflate = std::atoi(argv[++i]);
     else if (a == "-h" || a == "--help") { usage(argv[0]); return 0; }
     else pos.push_back(a);
   }

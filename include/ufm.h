@@ -255,6 +255,29 @@ int ufm_extract_path(ufm_t *p, int max_steps, int lookahead, int allow_indirect,
 int ufm_extract_paths_from(ufm_t *p, int n_starts, const float *starts_xy, int max_steps, int lookahead, int allow_indirect,
                            float *path_xy, int cap_points, float *step_costs, int cap_costs, ufm_path_info *info);
 
+/* ---- C-space inflation: the engine plans on the raster dilated by the vehicle's footprint (the reference's simulator does this on
+ * the host before the planner sees anything: cv2.getStructuringElement(MORPH_ELLIPSE, (cspace, cspace)) + cv2.dilate,
+ * Simulator/simulator/run_simulator.py:143,151,181-186, Tests/run_test.py:96-105,140-147).  The footprint is DATA, not a diameter: the
+ * caller hands over the matrix getStructuringElement (or anything else) produced -- mask[mh][mw], row-major uint8, non-zero = set, with
+ * an anchor (anchor_row, anchor_col); -1, -1: (mh / 2, mw / 2), OpenCV's default.  With a footprint set the engine keeps the caller's
+ * RAW raster per map and plans on
+ *     planning[i][j] = max { raw[i + a - anchor_row][j + b - anchor_col] : mask[a][b] != 0, the raw index inside the map }
+ * (cells outside the map are ignored: OpenCV's default border for dilate, and edge replication for a max).  Everything downstream reads
+ * the planning raster as before: the threshold, the operators, the path extractor, ufm_read_map, step deltas; ufm_stats::updated and
+ * expanded count elements seeded by cells of the PLANNING raster that changed.
+ * ufm_set_cspace: 1 <= mw, mh <= 31, the anchor inside the mask and the anchor cell set (so planning >= raw); a property of the vehicle,
+ * set after ufm_create and before the first ufm_set_map* -- UFM_ERR_INVALID otherwise.  A 1 x 1 mask is "off"; off is the default and
+ * costs nothing (no raw raster, no scratch, no launch, no other route).
+ * With a footprint, ufm_set_map* and ufm_patch_map* (and the batch forms) take RAW data.  A raw patch changes planning cells OUTSIDE its
+ * rectangle too: the engine writes it to the raw raster, dilates the grown rectangle -- rows [x - (mh-1-anchor_row), x+h-1 + anchor_row],
+ * columns [y - (mw-1-anchor_col), y+w-1 + anchor_col], clipped to the map: the mask reflected about its anchor -- and applies that as an
+ * ordinary patch, so "planning raster == dilate(raw raster)" holds exactly, at a cost proportional to the patch.  Such a patch is read at
+ * the call, stream-ordered: a host patch is not held for the replan's block kernel, a batch's device patch is not deferred ("defer_patches"
+ * is without effect) -- both would apply raw bytes to the planning raster.
+ * ufm_read_raw_map: the raster as the caller gave it, patches applied, row-major [length][width]; UFM_ERR_INVALID when no footprint is set. ---- */
+int ufm_set_cspace(ufm_t *p, const uint8_t *mask, int mw, int mh, int anchor_row, int anchor_col);
+int ufm_read_raw_map(ufm_t *p, uint8_t *host_map);
+
 /* ---- measurement hooks ---- */
 int ufm_set_profiling(ufm_t *p, int enable);   /* HIP-event timing of every relax launch */
 void *ufm_stream(ufm_t *p);                    /* hipStream_t the kernels run on */
@@ -285,7 +308,9 @@ int ufm_batch_patch_map(ufm_batch_t *b, int i, const uint8_t *host_patch, int x,
  * OPT-IN, ufm_batch_set_param(b, "defer_patches", 1): a patch of at most 4096 cells handed to a batch of more than one map is then applied
  * by ONE launch for all maps at the next ufm_batch_step (or ufm_batch_read_map / _extract_path / _set_map, whichever comes first), not at
  * the call -- one launch per round instead of one per map -- and the buffer must stay valid and unchanged until that call has returned
- * (bench.py turns it on: its patches sit in the receive buffer of the round's broadcast, reused two rounds later). */
+ * (bench.py turns it on: its patches sit in the receive buffer of the round's broadcast, reused two rounds later).
+ * With a footprint set (ufm_batch_set_cspace) a device patch is NOT deferred, whatever "defer_patches" says: it is raw data, read at the
+ * call, stream-ordered, like a single planner's. */
 int ufm_batch_patch_map_device(ufm_batch_t *b, int i, const uint8_t *dev_patch, int x, int y, int w, int h);
 int ufm_batch_set_start(ufm_batch_t *b, int i, float x, float y);
 int ufm_batch_set_goal(ufm_batch_t *b, int i, float x, float y);
@@ -301,6 +326,9 @@ void *ufm_batch_stream(ufm_batch_t *b, int shard);                         /* hi
 /* as ufm_track_changes / ufm_read_changes: tracking for every map of the batch, a read for map i alone (one scan of that map) */
 int ufm_batch_track_changes(ufm_batch_t *b, int enable);
 int ufm_batch_read_changes(ufm_batch_t *b, int i, int cap, int32_t *xy, float *g, int32_t *info, int *total);
+/* as ufm_set_cspace / ufm_read_raw_map: one footprint for every map on every shard, set before the first ufm_batch_set_map*; the raw raster of map i */
+int ufm_batch_set_cspace(ufm_batch_t *b, const uint8_t *mask, int mw, int mh, int anchor_row, int anchor_col);
+int ufm_batch_read_raw_map(ufm_batch_t *b, int i, uint8_t *host_map);
 /* all maps in one launch: path_xy [n_maps][cap_points][2], step_costs [n_maps][cap_costs], info [n_maps] */
 int ufm_batch_extract_path(ufm_batch_t *b, int max_steps, int lookahead, int allow_indirect,
                            float *path_xy, int cap_points, float *step_costs, int cap_costs, ufm_path_info *info);

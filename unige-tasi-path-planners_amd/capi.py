@@ -26,6 +26,7 @@ SYMBOLS = [
     "ufm_batch_patch_map_device", "ufm_batch_read_map", "ufm_batch_set_profiling", "ufm_batch_stream", "ufm_read_queue",
     "ufm_track_changes", "ufm_read_changes", "ufm_batch_track_changes", "ufm_batch_read_changes",
     "ufm_extract_paths_from", "ufm_batch_extract_paths_from",
+    "ufm_set_cspace", "ufm_read_raw_map", "ufm_batch_set_cspace", "ufm_batch_read_raw_map",
 ]
 
 
@@ -160,6 +161,10 @@ def load_library():
     L.ufm_read_changes.argtypes = [vp, i, vp, vp, vp, vp]
     L.ufm_batch_track_changes.argtypes = [vp, i]
     L.ufm_batch_read_changes.argtypes = [vp, i, i, vp, vp, vp, vp]
+    L.ufm_set_cspace.argtypes = [vp, vp, i, i, i, i]
+    L.ufm_read_raw_map.argtypes = [vp, vp]
+    L.ufm_batch_set_cspace.argtypes = [vp, vp, i, i, i, i]
+    L.ufm_batch_read_raw_map.argtypes = [vp, i, vp]
     _LIB = L
     return L
 
@@ -167,6 +172,24 @@ def load_library():
 def _chk(rc, what):
     if rc != 0:
         raise UfmError("%s failed with code %d" % (what, rc))
+
+
+def cspace_disc(diameter):
+    """The footprint harness.dilate(img, diameter) dilates by, as ufm_set_cspace takes it: a uint8 matrix of edge 2 * (diameter // 2) + 1
+    with the anchor at its centre -- the disc x^2 + y^2 <= r^2, r = diameter // 2 (diameter <= 1: the 1 x 1 mask, "off")."""
+    if diameter <= 1:
+        return np.ones((1, 1), np.uint8)
+    r = diameter // 2
+    yy, xx = np.mgrid[-r:r + 1, -r:r + 1]
+    return ((xx * xx) / max(r * r, 1) + (yy * yy) / max(r * r, 1) <= 1.0).astype(np.uint8)
+
+
+def _cspace_args(mask, anchor):
+    mask = np.ascontiguousarray(mask, dtype=np.uint8)
+    if mask.ndim != 2:
+        raise UfmError("a footprint is a matrix")
+    ar, ac = (-1, -1) if anchor is None else (int(anchor[0]), int(anchor[1]))
+    return mask, mask.shape[1], mask.shape[0], ar, ac
 
 
 def _read_changes(call, what, want_info, cap=None):
@@ -344,6 +367,18 @@ class Planner:
         _chk(self.L.ufm_read_map(self.h, m.ctypes.data), "ufm_read_map")
         return m
 
+    def set_cspace(self, mask, anchor=None):
+        """ufm_set_cspace: the vehicle's footprint (uint8 matrix, non-zero = set; anchor (row, col), None: the centre (mh // 2, mw // 2)).
+        Before the first set_map; from then on set_map / patch_map take the RAW raster and the engine plans on its dilation."""
+        mask, mw, mh, ar, ac = _cspace_args(mask, anchor)
+        _chk(self.L.ufm_set_cspace(self.h, mask.ctypes.data, mw, mh, ar, ac), "ufm_set_cspace")
+
+    def read_raw_map(self, width, length):
+        """the raster as the caller gave it, patches applied (read_map: the planning raster, its dilation); only with a footprint set"""
+        m = np.empty((length, width), dtype=np.uint8)
+        _chk(self.L.ufm_read_raw_map(self.h, m.ctypes.data), "ufm_read_raw_map")
+        return m
+
     def check_layout(self):
         """(ring entries, cost-window bytes) that differ from the values they copy; (0, 0) when sound"""
         bad = (C.c_uint64 * 2)()
@@ -453,6 +488,16 @@ class BatchPlanner:
     def read_map(self, i, width, length):
         m = np.empty((length, width), dtype=np.uint8)
         _chk(self.L.ufm_batch_read_map(self.h, i, m.ctypes.data), "ufm_batch_read_map")
+        return m
+
+    def set_cspace(self, mask, anchor=None):
+        """as Planner.set_cspace, for every map on every shard"""
+        mask, mw, mh, ar, ac = _cspace_args(mask, anchor)
+        _chk(self.L.ufm_batch_set_cspace(self.h, mask.ctypes.data, mw, mh, ar, ac), "ufm_batch_set_cspace")
+
+    def read_raw_map(self, i, width, length):
+        m = np.empty((length, width), dtype=np.uint8)
+        _chk(self.L.ufm_batch_read_raw_map(self.h, i, m.ctypes.data), "ufm_batch_read_raw_map")
         return m
 
     def set_start(self, i, x, y):

@@ -28,6 +28,7 @@
 #include <climits>
 #include <cmath>
 #include <cstddef>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -46,6 +47,7 @@ namespace {
 #include "ufm_control.h"
 
 #include "ufm_region.h"
+#include "ufm_cspace.h"
 
 #include "ufm_host.h"
 #include "ufm_delta.h"
@@ -238,6 +240,8 @@ static int engine_read_map(Engine *e, int m, uint8_t *host_map) {
     return UFM_OK;
 }
 int ufm_read_map(ufm_t *p, uint8_t *host_map) { return p ? engine_read_map(p->e, 0, host_map) : UFM_ERR_INVALID; }
+int ufm_set_cspace(ufm_t *p, const uint8_t *mask, int mw, int mh, int anchor_row, int anchor_col) { return p ? engine_set_cspace(p->e, mask, mw, mh, anchor_row, anchor_col) : UFM_ERR_INVALID; }
+int ufm_read_raw_map(ufm_t *p, uint8_t *host_map) { return p ? engine_read_raw_map(p->e, 0, host_map) : UFM_ERR_INVALID; }
 static int engine_set_param(Engine *e, const char *name, double value) {
     if (!e || !name) return UFM_ERR_INVALID;
     if (!std::strcmp(name, "delta")) e->delta_abs = (float)value;
@@ -394,6 +398,13 @@ int ufm_batch_step(ufm_batch_t *b, ufm_stats *stats) {
 }
 int ufm_batch_read_field(ufm_batch_t *b, int i, int x0, int y0, int nx, int ny, float *g, float *rhs) { UFM_BATCH_MAP(b, i); return engine_read_field(e, li, x0, y0, nx, ny, g, rhs); }
 int ufm_batch_read_map(ufm_batch_t *b, int i, uint8_t *host_map) { UFM_BATCH_MAP(b, i); return engine_read_map(e, li, host_map); }
+int ufm_batch_read_raw_map(ufm_batch_t *b, int i, uint8_t *host_map) { UFM_BATCH_MAP(b, i); return engine_read_raw_map(e, li, host_map); }
+int ufm_batch_set_cspace(ufm_batch_t *b, const uint8_t *mask, int mw, int mh, int anchor_row, int anchor_col) {
+    if (!b || b->shards.empty()) return UFM_ERR_INVALID;
+    for (Engine *e : b->shards) for (const MapState &ms : e->maps) if (ms.have_map) return UFM_ERR_INVALID;   // (all shards or none)
+    for (Engine *e : b->shards) { const int rc = engine_set_cspace(e, mask, mw, mh, anchor_row, anchor_col); if (rc != UFM_OK) return rc; }
+    return UFM_OK;
+}
 int ufm_batch_set_profiling(ufm_batch_t *b, int enable) {
     if (!b) return UFM_ERR_INVALID;
     for (Engine *e : b->shards) e->profiling = enable != 0;

@@ -250,6 +250,16 @@ struct Engine {
     int patch_lazy(int m, const uint8_t *host_patch, int x, int y, int w, int h, bool *taken);
     int flush_lazy();
     int ensure_pmask(size_t n);
+    // C-space inflation (ufm_set_cspace; ufm_cspace.h).  Off -- the default, and a 1 x 1 mask -- nothing below exists or runs.
+    // On: d_raw holds the caller's raster per map, P.cost its dilation by the footprint; a raw patch goes to d_raw, the rectangle of P.cost it
+    // can change is dilated into d_cs_patch and handed to patch() as an ordinary patch -- never held for the block kernel, never deferred,
+    // both of which would apply raw bytes to the planning raster.
+    CspaceMask cs;
+    uint8_t *d_raw = nullptr;        // [nmaps][L][W]
+    uint8_t *d_cs_patch = nullptr;   // the dilated grown rectangle of the patch being applied, dense
+    size_t d_cs_patch_cap = 0;
+    void cspace_dilate(int m, uint8_t *out, int pitch, const PatchRect &r);
+    int patch_raw(int m, const uint8_t *dev_patch, int x, int y, int w, int h);
     void patch_small(int m, const uint8_t *src, int x, int y, int w, int h) {
         with_elements(algo, [&](auto nodes) { k_patch_small<nodes()><<<1, 1024, 0, stream>>>(P, m, src, d_pmask, x, y, w, h); });
     }
@@ -278,6 +288,8 @@ void Engine::release() {
                     P.queued, P.prio, P.start, P.bnd, P.dyn, P.spos, P.touched, P.fresh, P.tlist, P.sflag, P.slist, P.slist2,
                     P.mark, P.num_updated, P.consume, P.lmax, P.own_prio, P.own_lock, P.own_min, P.ctr, d_scratch};
     for (void *q : ptrs) if (q) hipFree(q);
+    if (d_raw) hipFree(d_raw);
+    d_raw = nullptr;
     P = DevParams{};                     // every pointer null again: a failed alloc() can be released, and released twice
     d_scratch = nullptr;
     allocated = false;
@@ -347,6 +359,7 @@ int Engine::alloc(int width, int length) {
     dmalloc(P.own_min, sizeof(int) * OWN_NW);
     dmalloc(P.ctr, sizeof(DevCounters));
     dmalloc(d_scratch, sizeof(int) * (4 * nmaps + 16));
+    if (cs.on) dmalloc(d_raw, P.cstride * nmaps);
     if (rc != UFM_OK) { release(); return rc; }
     rc = [&]() -> int {
         // (the lists: a slot that was never written must still read as a tile id -- an in-launch reader may look at a slot its writer has claimed
@@ -678,6 +691,7 @@ int Engine::patch_lazy(int m, const uint8_t *host_patch, int x, int y, int w, in
     *taken = false;
     if (m < 0 || m >= nmaps || !allocated || !maps[m].have_map) return UFM_ERR_INVALID;
     if (x < 0 || y < 0 || w <= 0 || h <= 0 || x + h > L || y + w > W) return UFM_ERR_INVALID;   // Graph.cpp:38-41
+    if (cs.on) return UFM_OK;          // (a footprint: the block kernel would apply raw bytes to the planning raster)
     if (!(lazy_patches && nmaps == 1 && use_region && fuse_control && spin_wait && w <= 64 && h <= 64)) return UFM_OK;
     if ((int)lazy.size() >= LAZY_SLOTS || pending.size() != lazy.size()) return UFM_OK;      // (only behind other held patches: the block kernel applies them in order)
     if (!h_lazy) HIPCHK(hipHostMalloc(&h_lazy, (size_t)LAZY_SLOTS * 4096, hipHostMallocMapped));
@@ -721,6 +735,36 @@ int Engine::patch(int m, const uint8_t *dev_patch, int x, int y, int w, int h, b
     HIPCHK(hipGetLastError());
     pending.push_back({m, x, y, w, h});
     return UFM_OK;
+}
+
+// ---- C-space inflation: planning raster == dilate(raw raster), kept at a cost proportional to the patch ----
+void Engine::cspace_dilate(int m, uint8_t *out, int pitch, const PatchRect &r) {
+    CspaceJob j{};
+    j.raw = d_raw + (size_t)m * P.cstride; j.out = out;
+    j.L = L; j.W = W; j.x0 = r.x; j.y0 = r.y; j.h = r.h; j.w = r.w; j.pitch = pitch;
+    j.mh = cs.mh; j.mw = cs.mw; j.ar = cs.ar; j.ac = cs.ac;
+    for (int a = 0; a < CSPACE_MAX; ++a) j.rows[a] = cs.rows[a];
+    k_cspace_dilate<<<dim3((r.w + CS_TC - 1) / CS_TC, (r.h + CS_TR - 1) / CS_TR), 256, 0, stream>>>(j);
+}
+// a raw patch with a footprint set, stream-ordered: into the raw store, the grown rectangle dilated into the scratch patch, that one
+// through patch() -- which detects the cells of the planning raster that really changed, seeds from them and keeps the cost windows in step
+int Engine::patch_raw(int m, const uint8_t *dev_patch, int x, int y, int w, int h) {
+    if (m < 0 || m >= nmaps || !allocated || !maps[m].have_map) return UFM_ERR_INVALID;
+    if (x < 0 || y < 0 || w <= 0 || h <= 0 || x + h > L || y + w > W) return UFM_ERR_INVALID;   // Graph.cpp:38-41
+    const PatchRect g = grow_rect(PatchRect{m, x, y, w, h}, cs.mh, cs.mw, cs.ar, cs.ac, L, W);
+    const size_t n = (size_t)g.w * g.h;
+    if (n > d_cs_patch_cap) {
+        const size_t cap = std::max<size_t>(n, 4096);
+        { int rc = regrow(stream, cap, d_cs_patch_cap, cap, d_cs_patch); if (rc != UFM_OK) return rc; }
+    }
+    // (everything patch() does that can fail -- applying what is held, the mask buffer's growth -- comes before the first write to the raw
+    //  store: a call that returns an error has left both rasters as they were)
+    { int rc = flush_deferred(); if (rc != UFM_OK) return rc; }
+    { int rc = ensure_pmask(n); if (rc != UFM_OK) return rc; }
+    k_raw_store<<<(w * h + 255) / 256, 256, 0, stream>>>(d_raw + (size_t)m * P.cstride, W, dev_patch, x, y, w, h);
+    cspace_dilate(m, d_cs_patch, g.w, g);
+    HIPCHK(hipGetLastError());
+    return patch(m, d_cs_patch, g.x, g.y, g.w, g.h);
 }
 
 // ---- a step: ReplannerBase::step (ReplannerBase.h:43-75) --------------------------------------------------------------------
@@ -1240,7 +1284,7 @@ int engine_destroy(Engine *e) {
     for (hipEvent_t v : e->own_ev) if (v) hipEventDestroy(v);
     for (hipEvent_t v : e->reg_ev) if (v) hipEventDestroy(v);
     for (hipEvent_t v : e->trk_ev) if (v) hipEventDestroy(v);
-    free_all(hipFree, e->d_patch, e->d_pmask, e->d_field, e->d_info, e->d_jobs, e->d_path);
+    free_all(hipFree, e->d_cs_patch, e->d_patch, e->d_pmask, e->d_field, e->d_info, e->d_jobs, e->d_path);
     free_all(hipHostFree, e->h_jobs, e->h_path, e->h_patch, e->h_lazy);
     e->drop_graphs();
     free_all(hipHostFree, e->h_ctr, e->h_pipe_ctr[0], e->h_pipe_ctr[1], e->h_job, e->scratch.acc, e->h_bnd);
@@ -1260,8 +1304,10 @@ int engine_set_map(Engine *e, int m, const uint8_t *src, bool on_device, int wid
         int rc = e->alloc(width, length);
         if (rc != UFM_OK) return rc;
     }
-    HIPCHK(hipMemcpyAsync(e->P.cost + (size_t)m * e->P.cstride, src, (size_t)width * length,
+    // (a footprint: the input is the raw raster -- kept, and dilated into the planning raster before anything reads that one)
+    HIPCHK(hipMemcpyAsync((e->cs.on ? e->d_raw : e->P.cost) + (size_t)m * e->P.cstride, src, (size_t)width * length,
                           on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, e->stream));
+    if (e->cs.on) e->cspace_dilate(m, e->P.cost + (size_t)m * e->P.cstride, width, PatchRect{m, 0, 0, width, length});
     k_cost_windows<<<2048, 256, 0, e->stream>>>(e->P, m);
     {   // mean traversable cost -> default ordering band
         unsigned long long *d_acc = reinterpret_cast<unsigned long long *>(e->d_scratch);
@@ -1283,7 +1329,7 @@ int engine_set_map(Engine *e, int m, const uint8_t *src, bool on_device, int wid
 int engine_patch(Engine *e, int m, const uint8_t *src, bool on_device, int x, int y, int w, int h) {
     if (!e || !src) return UFM_ERR_INVALID;
     HIPCHK(hipSetDevice(e->device));
-    if (on_device) return e->patch(m, src, x, y, w, h, true);
+    if (on_device) return e->cs.on ? e->patch_raw(m, src, x, y, w, h) : e->patch(m, src, x, y, w, h, true);
     if (w <= 0 || h <= 0) return UFM_ERR_INVALID;
     {   // a small patch of a single planner: held in pinned memory for the replan's block kernel (Engine::patch_lazy)
         bool taken = false;
@@ -1299,7 +1345,24 @@ int engine_patch(Engine *e, int m, const uint8_t *src, bool on_device, int x, in
     }
     std::memcpy(e->h_patch, src, n);
     HIPCHK(hipMemcpyAsync(e->d_patch, e->h_patch, n, hipMemcpyHostToDevice, e->stream));
-    return e->patch(m, e->d_patch, x, y, w, h);
+    return e->cs.on ? e->patch_raw(m, e->d_patch, x, y, w, h) : e->patch(m, e->d_patch, x, y, w, h);
+}
+
+// ufm_set_cspace / ufm_batch_set_cspace: a property of the vehicle, set before the first raster
+int engine_set_cspace(Engine *e, const uint8_t *mask, int mw, int mh, int ar, int ac) {
+    if (!e) return UFM_ERR_INVALID;
+    for (const MapState &ms : e->maps) if (ms.have_map) return UFM_ERR_INVALID;
+    if (!cspace_pack(mask, mw, mh, ar, ac, &e->cs)) return UFM_ERR_INVALID;
+    // (arrays without a map -- a ufm_set_map that failed after its allocation -- were sized without the raw store: the next one allocates anew)
+    if (e->allocated) { HIPCHK(hipSetDevice(e->device)); e->release(); }
+    return UFM_OK;
+}
+int engine_read_raw_map(Engine *e, int m, uint8_t *host_map) {
+    if (!e || !host_map || !e->cs.on || !e->allocated || m < 0 || m >= e->nmaps || !e->maps[m].have_map) return UFM_ERR_INVALID;
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipMemcpyAsync(host_map, e->d_raw + (size_t)m * e->P.cstride, e->P.cstride, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return UFM_OK;
 }
 
 int engine_set_goal(Engine *e, int m, float x, float y) {

@@ -166,7 +166,7 @@ class Pipes:
 
 def run_mission(cmd, pipe_to_planner, pipe_from_planner, img_h, start, goal, radius=5, cspace_diameter=1,
                 low_res_penalty=10, use_heuristic=False, max_moves=10000, on_map=None, on_move=None, display_shift=0.0,
-                append_pipes=True, tof=False, on_expanded=None):
+                append_pipes=True, tof=False, on_expanded=None, planner_inflates=False):
     """One mission as Tests/run_test.py:85-177 runs it: launch the planner process `cmd`, send the
     C-space of the low-resolution map, then per robot position reveal the disc of radius `radius`,
     send its bounding patch and the heuristic hint, receive the planned path.  start / goal are
@@ -175,7 +175,9 @@ def run_mission(cmd, pipe_to_planner, pipe_from_planner, img_h, start, goal, rad
     on_map(cspace, min_cost) is called with what the planner receives first;
     on_move(i, position, top, left, patch, min_cost, (path, costs, dist, cost, times)) after every reply
     (position without `display_shift`, the half cell the DFM driver adds for display); with tof the planner is asked for its dump of the
-    expanded elements after every step and on_expanded(i, records) gets it (Pipes.receive_expanded).  Returns the list of positions visited and whether the planner reported the end."""
+    expanded elements after every step and on_expanded(i, records) gets it (Pipes.receive_expanded).
+    planner_inflates: the planner process dilates on its own (ufm_planner --inflate D with D = cspace_diameter): the low-resolution map and
+    the patches are sent RAW, and on_map / on_move get what was sent; min_cost is still taken from the inflated map.  Returns the list of positions visited and whether the planner reported the end."""
     for p in (pipe_to_planner, pipe_from_planner):
         if not os.path.exists(p):
             os.mkfifo(p)
@@ -193,13 +195,13 @@ def run_mission(cmd, pipe_to_planner, pipe_from_planner, img_h, start, goal, rad
         min_cost = int(cspace.min())
         height, width = cspace.shape
         io.send("ii", width, height)
-        io.send_bytes(np.ascontiguousarray(cspace).tobytes())
+        io.send_bytes(np.ascontiguousarray(data_l if planner_inflates else cspace).tobytes())
         if start is not None:
             io.send("ffffB", float(start[0]), float(start[1]), float(goal[0]), float(goal[1]), 1 if tof else 0)
         io.send("i", min_cost)
         io.flush()
         if on_map is not None:
-            on_map(cspace.copy(), min_cost)
+            on_map(data_l.copy() if planner_inflates else cspace.copy(), min_cost)
         prev = None
         while len(trace) < max_moves:
             (code,) = io.recv("b")
@@ -216,7 +218,7 @@ def run_mission(cmd, pipe_to_planner, pipe_from_planner, img_h, start, goal, rad
             center = (int(round(yr)), int(round(xr)))         # (col, row) of the position as received, run_test.py:143
             data_l, (top, left), ranges = round_patch_update(data_l, data_h, center, radius)
             cspace = dilate(data_l, cspace_diameter)
-            patch = np.ascontiguousarray(cspace[ranges[0], ranges[1]])
+            patch = np.ascontiguousarray((data_l if planner_inflates else cspace)[ranges[0], ranges[1]])
             if use_heuristic:
                 min_cost = int(cspace.min())
             io.send("b", 1)

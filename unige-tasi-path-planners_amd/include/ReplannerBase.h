@@ -63,6 +63,12 @@ class ReplannerBase {
   void set_occupancy_threshold(float threshold) { grid.set_occupancy_threshold(threshold); check(ufm_set_occupancy_threshold(handle_, threshold)); }
   void set_heuristic_multiplier(float mult) { heuristic_multiplier = mult; check(ufm_set_heuristic_multiplier(handle_, mult)); }
 
+  /** C-space inflation on the device (ufm_set_cspace; no reference counterpart: the reference's simulator dilates on the host): the
+   *  vehicle's footprint mask[mh][mw] with its anchor (-1, -1: the centre), before the first set_map.  set_map / patch_map then take the
+   *  RAW raster; `grid` keeps holding that raw raster, the engine plans (and the extractor walks) on its dilation. */
+  void set_cspace(const uint8_t *mask, int mw, int mh, int anchor_row = -1, int anchor_col = -1) {
+    check(ufm_set_cspace(handle_, mask, mw, mh, anchor_row, anchor_col));
+  }
   void set_map(const std::shared_ptr<uint8_t> &new_map, int w, int h) {
     grid.init(new_map, w, h);
     check(ufm_set_map(handle_, new_map.get(), w, h));
