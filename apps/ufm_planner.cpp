@@ -12,13 +12,16 @@
 // LinearInterpolationPathExtractor, reset / set_* / patch_map / step / extract_path, u_time,
 // p_time, e_time, map.size(), map.buckets.
 //
-//   ufm_planner [--planner FD|SG|DFM] [--level K] [--max-moves N] [--verify-follow] [--inflate D] <fifo_in> <fifo_out>
+//   ufm_planner [--planner FD|SG|DFM] [--level K] [--max-moves N] [--verify-follow] [--inflate D] [--auto-heuristic] <fifo_in> <fifo_out>
 //        start, goal and the `tof` flag arrive in-band after the map (DFM/main.cpp:62-67)
 //   ufm_planner [...] <mapfile> <from_x> <from_y> <to_x> <to_y> <cspace> <fifo_in> <fifo_out> <gui> <tof> <outpath>
 //        the 11-argument form of FDSTAR/main.cpp:16-31 and SGDFM/main.cpp
 // --inflate D: the map and the patches on the wire are RAW and the engine plans on their dilation by the disc of diameter D
 // (ufm_set_cspace; x^2 + y^2 <= (D / 2)^2 on a (2 (D / 2) + 1)-cell square, the footprint of the Python harness' dilate) -- the simulator
 // then need not inflate anything.  The positional <cspace> stays as inert as it is in the reference drivers.
+// --auto-heuristic: the heuristic multiplier is the smallest cost of the planning raster as the engine holds it (the cost census,
+// ufm_track_costs + "auto_multiplier"); the wire's min_cost is read, as the protocol demands, and not used -- with --inflate the simulator
+// then need not know the inflated map at all.
 // With `tof` the expanded-element dump after every step is kept up to date from the steps' deltas (ExpandedMap::follow_changes), not
 // read back whole; --verify-follow also builds it the old way every step -- a read of the whole field through a second view of the
 // same planner -- and ends the run (exit code 3) if the two differ in any element, value, Info or order.
@@ -76,6 +79,7 @@ struct Options {
   bool tof = false;
   bool verify_follow = false;
   int inflate = 0;           // --inflate D: footprint diameter (<= 1: off)
+  bool auto_heuristic = false;   // --auto-heuristic: the multiplier follows the engine's planning raster
   std::string fifo_in, fifo_out;
 };
 
@@ -110,6 +114,7 @@ int serve(Options opt, bool cell_planner, bool indirect) {
   planner.reset();
   planner.set_occupancy_threshold(1);
   planner.set_heuristic_multiplier((float)min_cost);
+  if (opt.auto_heuristic) planner.set_auto_heuristic(true);
   if (opt.inflate > 1) {
     const int r = opt.inflate / 2, n = 2 * r + 1;
     if (n > 31) throw std::runtime_error("--inflate: the footprint is at most 31 cells wide");
@@ -142,7 +147,7 @@ int serve(Options opt, bool cell_planner, bool indirect) {
     io.get_bytes(patch.get(), (size_t)pw * ph);
     if (pw > 0 && ph > 0) planner.patch_map(patch, top, left, pw, ph);
     min_cost = io.get<int32_t>();
-    planner.set_heuristic_multiplier((float)min_cost);
+    if (!opt.auto_heuristic) planner.set_heuristic_multiplier((float)min_cost);
 
     const int rc = planner.step();
     if (rc != LOOP_OK) throw std::runtime_error("step() returned " + std::to_string(rc));
@@ -198,7 +203,7 @@ int serve(Options opt, bool cell_planner, bool indirect) {
 
 void usage(const char *argv0) {
   std::fprintf(stderr,
-               "Usage:\n\t%s [--planner FD|SG|DFM] [--level K] [--max-moves N] [--verify-follow] [--inflate D] <fifo_in> <fifo_out>\n"
+               "Usage:\n\t%s [--planner FD|SG|DFM] [--level K] [--max-moves N] [--verify-follow] [--inflate D] [--auto-heuristic] <fifo_in> <fifo_out>\n"
                "\t%s [...] <mapfile> <from_x> <from_y> <to_x> <to_y> <cspace> <fifo_in> <fifo_out> <gui> <tof> <outpath>\n",
                argv0, argv0);
 }
@@ -229,6 +234,7 @@ int main(int argc, char **argv) {
     else if (a == "--max-moves" && i + 1 < argc) opt.max_moves = std::atol(argv[++i]);
     else if (a == "--verify-follow") opt.verify_follow = true;
     else if (a == "--inflate" && i + 1 < argc) opt.inflate = std::atoi(argv[++i]);
+    else if (a == "--auto-heuristic") opt.auto_heuristic = true;
     else if (a == "-h" || a == "--help") { usage(argv[0]); return 0; }
     else pos.push_back(a);
   }

@@ -278,6 +278,35 @@ int ufm_extract_paths_from(ufm_t *p, int n_starts, const float *starts_xy, int m
 int ufm_set_cspace(ufm_t *p, const uint8_t *mask, int mw, int mh, int anchor_row, int anchor_col);
 int ufm_read_raw_map(ufm_t *p, uint8_t *host_map);
 
+/* ---- cost census: what the planning raster holds, and the heuristic multiplier that follows it.  Every move of the reference's wire
+ * protocol carries the planning raster's smallest cost -- cv2.minMaxLoc(data_l_cspace)[0], Simulator/simulator/run_simulator.py:152,183 --
+ * and the driver sets it as the heuristic multiplier: set_heuristic_multiplier((float)min_cost), Tests/Planners/DFM/main.cpp:111-112,
+ * FDSTAR/main.cpp:86,121.  With ufm_set_cspace only the engine holds that raster; this is how it says what is in it.
+ * OPT-IN: off by default, and off costs nothing -- no allocation, no launch, no other route.
+ * ufm_track_costs(p, 1) gives every map 256 counters, hist[v] = the number of cells of the map's PLANNING raster (what ufm_read_map returns:
+ * the dilated one if a footprint is set) whose value is v.  EXACT means: between any two calls of this header hist equals a count over
+ * ufm_read_map's raster, cell for cell -- sum(hist) == length * width, and the smallest / largest v with hist[v] != 0 are the raster's own
+ * minimum and maximum, lethal cells included, as minMaxLoc gives them.  Built by one pass when a raster is set (ufm_set_map*, after the
+ * dilation; turning tracking on with maps already set builds from the rasters as they stand), corrected at every patch at a cost
+ * proportional to the patch -- with a footprint that is the grown rectangle: the cells OUTSIDE the patch that its dilation changes are
+ * counted too.  A minimum that RISES because a patch removed the cheapest cell is therefore reported, which a running minimum cannot do.
+ * ufm_reset leaves the census alone (the raster is unchanged); ufm_track_costs(p, 0) frees it (UFM_ERR_INVALID while "auto_multiplier" is 1).
+ * DECLINED while the census is on, exactly as with a footprint: the two routes that apply a patch later than the call.  A single planner's
+ * small host patch is not held for the replan's block kernel but staged and applied at the call; a batch's "defer_patches" is accepted and
+ * WITHOUT EFFECT, every device patch is read at the call, stream-ordered.  Results do not change, only the route.
+ * ufm_read_cost_census: hist (may be NULL) and the smallest / largest value present (may be NULL); UFM_ERR_INVALID for a NULL handle, with
+ * tracking off, or with no map set.
+ * ufm_set_param(p, "auto_multiplier", 1) (default 0; turns the census on if it is off): from then on every ufm_step uses (float)min_cost of
+ * the planning raster as it stands when the step begins -- every patch handed over before it counted -- where it would use the caller's
+ * multiplier; ufm_set_heuristic_multiplier is stored and ignored until the parameter is 0 again.  The value travels to the device like any
+ * new multiplier, through memory: ufm_stats::graphs_instantiated does not grow with it.  Accepted without effect by a planner created with
+ * use_heuristic = 0 (its keys have no heuristic term; no step waits for the census then).  A batch has one multiplier: the minimum over
+ * ALL maps of the batch, all shards included -- admissible for every map, and independent of how the maps are spread.
+ * ufm_heuristic_multiplier: the multiplier the last step selected, the caller's or the automatic one (before the first step: the caller's). ---- */
+int ufm_track_costs(ufm_t *p, int enable);
+int ufm_read_cost_census(ufm_t *p, uint64_t hist[256], int *min_cost, int *max_cost);
+int ufm_heuristic_multiplier(ufm_t *p, float *used);
+
 /* ---- measurement hooks ---- */
 int ufm_set_profiling(ufm_t *p, int enable);   /* HIP-event timing of every relax launch */
 void *ufm_stream(ufm_t *p);                    /* hipStream_t the kernels run on */
@@ -310,7 +339,7 @@ int ufm_batch_patch_map(ufm_batch_t *b, int i, const uint8_t *host_patch, int x,
  * the call -- one launch per round instead of one per map -- and the buffer must stay valid and unchanged until that call has returned
  * (bench.py turns it on: its patches sit in the receive buffer of the round's broadcast, reused two rounds later).
  * With a footprint set (ufm_batch_set_cspace) a device patch is NOT deferred, whatever "defer_patches" says: it is raw data, read at the
- * call, stream-ordered, like a single planner's. */
+ * call, stream-ordered, like a single planner's.  The same holds while the cost census is on (ufm_batch_track_costs). */
 int ufm_batch_patch_map_device(ufm_batch_t *b, int i, const uint8_t *dev_patch, int x, int y, int w, int h);
 int ufm_batch_set_start(ufm_batch_t *b, int i, float x, float y);
 int ufm_batch_set_goal(ufm_batch_t *b, int i, float x, float y);
@@ -329,6 +358,12 @@ int ufm_batch_read_changes(ufm_batch_t *b, int i, int cap, int32_t *xy, float *g
 /* as ufm_set_cspace / ufm_read_raw_map: one footprint for every map on every shard, set before the first ufm_batch_set_map*; the raw raster of map i */
 int ufm_batch_set_cspace(ufm_batch_t *b, const uint8_t *mask, int mw, int mh, int anchor_row, int anchor_col);
 int ufm_batch_read_raw_map(ufm_batch_t *b, int i, uint8_t *host_map);
+/* as ufm_track_costs / ufm_read_cost_census / ufm_heuristic_multiplier: tracking for every map on every shard; the census of map i, or
+ * with i = -1 the sum over all maps of all shards (every map needs a raster); UFM_ERR_INVALID for any other i outside the batch.  The
+ * batch's automatic multiplier is the minimum of the i = -1 census. */
+int ufm_batch_track_costs(ufm_batch_t *b, int enable);
+int ufm_batch_read_cost_census(ufm_batch_t *b, int i, uint64_t hist[256], int *min_cost, int *max_cost);
+int ufm_batch_heuristic_multiplier(ufm_batch_t *b, float *used);
 /* all maps in one launch: path_xy [n_maps][cap_points][2], step_costs [n_maps][cap_costs], info [n_maps] */
 int ufm_batch_extract_path(ufm_batch_t *b, int max_steps, int lookahead, int allow_indirect,
                            float *path_xy, int cap_points, float *step_costs, int cap_costs, ufm_path_info *info);

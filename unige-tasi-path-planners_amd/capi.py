@@ -27,6 +27,8 @@ SYMBOLS = [
     "ufm_track_changes", "ufm_read_changes", "ufm_batch_track_changes", "ufm_batch_read_changes",
     "ufm_extract_paths_from", "ufm_batch_extract_paths_from",
     "ufm_set_cspace", "ufm_read_raw_map", "ufm_batch_set_cspace", "ufm_batch_read_raw_map",
+    "ufm_track_costs", "ufm_read_cost_census", "ufm_heuristic_multiplier",
+    "ufm_batch_track_costs", "ufm_batch_read_cost_census", "ufm_batch_heuristic_multiplier",
 ]
 
 
@@ -165,6 +167,12 @@ def load_library():
     L.ufm_read_raw_map.argtypes = [vp, vp]
     L.ufm_batch_set_cspace.argtypes = [vp, vp, i, i, i, i]
     L.ufm_batch_read_raw_map.argtypes = [vp, i, vp]
+    L.ufm_track_costs.argtypes = [vp, i]
+    L.ufm_read_cost_census.argtypes = [vp, vp, C.POINTER(i), C.POINTER(i)]
+    L.ufm_heuristic_multiplier.argtypes = [vp, C.POINTER(f)]
+    L.ufm_batch_track_costs.argtypes = [vp, i]
+    L.ufm_batch_read_cost_census.argtypes = [vp, i, vp, C.POINTER(i), C.POINTER(i)]
+    L.ufm_batch_heuristic_multiplier.argtypes = [vp, C.POINTER(f)]
     _LIB = L
     return L
 
@@ -190,6 +198,14 @@ def _cspace_args(mask, anchor):
         raise UfmError("a footprint is a matrix")
     ar, ac = (-1, -1) if anchor is None else (int(anchor[0]), int(anchor[1]))
     return mask, mask.shape[1], mask.shape[0], ar, ac
+
+
+def _read_census(call, what):
+    """ufm_read_cost_census / ufm_batch_read_cost_census through `call(hist, min, max)`: (hist uint64 [256], min_cost, max_cost)"""
+    hist = np.zeros(256, np.uint64)
+    mn, mx = C.c_int(0), C.c_int(0)
+    _chk(call(hist.ctypes.data, C.byref(mn), C.byref(mx)), what)
+    return hist, mn.value, mx.value
 
 
 def _read_changes(call, what, want_info, cap=None):
@@ -379,6 +395,20 @@ class Planner:
         _chk(self.L.ufm_read_raw_map(self.h, m.ctypes.data), "ufm_read_raw_map")
         return m
 
+    def track_costs(self, on=True):
+        """the cost census (ufm_track_costs): 256 exact counters of the planning raster's values, kept under patches"""
+        _chk(self.L.ufm_track_costs(self.h, int(on)), "ufm_track_costs")
+
+    def read_cost_census(self):
+        """(hist uint64 [256], min_cost, max_cost) of the planning raster as it stands"""
+        return _read_census(lambda *a: self.L.ufm_read_cost_census(self.h, *a), "ufm_read_cost_census")
+
+    def heuristic_multiplier(self):
+        """the multiplier the last step used: the caller's, or with set_param("auto_multiplier", 1) the census' minimum"""
+        v = C.c_float(0.0)
+        _chk(self.L.ufm_heuristic_multiplier(self.h, C.byref(v)), "ufm_heuristic_multiplier")
+        return v.value
+
     def check_layout(self):
         """(ring entries, cost-window bytes) that differ from the values they copy; (0, 0) when sound"""
         bad = (C.c_uint64 * 2)()
@@ -499,6 +529,19 @@ class BatchPlanner:
         m = np.empty((length, width), dtype=np.uint8)
         _chk(self.L.ufm_batch_read_raw_map(self.h, i, m.ctypes.data), "ufm_batch_read_raw_map")
         return m
+
+    def track_costs(self, on=True):
+        """as Planner.track_costs, for every map on every shard"""
+        _chk(self.L.ufm_batch_track_costs(self.h, int(on)), "ufm_batch_track_costs")
+
+    def read_cost_census(self, i=-1):
+        """as Planner.read_cost_census, for map i; -1: all maps of the batch, summed"""
+        return _read_census(lambda *a: self.L.ufm_batch_read_cost_census(self.h, int(i), *a), "ufm_batch_read_cost_census")
+
+    def heuristic_multiplier(self):
+        v = C.c_float(0.0)
+        _chk(self.L.ufm_batch_heuristic_multiplier(self.h, C.byref(v)), "ufm_batch_heuristic_multiplier")
+        return v.value
 
     def set_start(self, i, x, y):
         _chk(self.L.ufm_batch_set_start(self.h, i, float(x), float(y)), "ufm_batch_set_start")

@@ -48,6 +48,7 @@ namespace {
 
 #include "ufm_region.h"
 #include "ufm_cspace.h"
+#include "ufm_census.h"
 
 #include "ufm_host.h"
 #include "ufm_delta.h"
@@ -263,6 +264,10 @@ static int engine_set_param(Engine *e, const char *name, double value) {
     else if (!std::strcmp(name, "owned_flags")) e->owned_flags = (int)value;
     else if (!std::strcmp(name, "owned_waves")) e->owned_waves = (int)value;
     else if (!std::strcmp(name, "defer_patches")) { if (e->allocated) { int rc = e->flush_deferred(); if (rc != UFM_OK) return rc; } e->defer_patches = value != 0; }
+    else if (!std::strcmp(name, "auto_multiplier")) {         // the census' minimum as the heuristic multiplier; 1 turns the census on
+        if (value != 0.0) { const int rc = engine_track_costs(e, 1); if (rc != UFM_OK) return rc; }
+        e->auto_multiplier = value != 0.0;
+    }
     else if (!std::strcmp(name, "region_debug")) e->region_debug = (int)value;
     else if (!std::strcmp(name, "region_band")) e->region_band = (float)value;
     else if (!std::strcmp(name, "region_ahead")) e->region_ahead = (int)value;
@@ -291,6 +296,25 @@ int ufm_batch_set_param(ufm_batch_t *b, const char *name, double value) {
     for (Engine *e : b->shards) { const int rc = engine_set_param(e, name, value); if (rc != UFM_OK) return rc; }
     return UFM_OK;
 }
+// the census of the engines' maps `first` .. `first + count - 1` (numbered through the shards, `per` to a shard), summed
+static int census_sum(Engine *const *shards, int per, int first, int count, uint64_t hist[256], int *min_cost, int *max_cost) {
+    uint64_t acc[CENSUS_BINS] = {};
+    for (int i = first; i < first + count; ++i) {
+        uint32_t h[CENSUS_BINS];
+        const int rc = engine_read_census(shards[i / per], i % per, h);
+        if (rc != UFM_OK) return rc;
+        for (int v = 0; v < CENSUS_BINS; ++v) acc[v] += h[v];
+    }
+    int mn = CENSUS_BINS, mx = -1;
+    for (int v = 0; v < CENSUS_BINS; ++v) if (acc[v]) { mn = std::min(mn, v); mx = v; }
+    if (hist) std::memcpy(hist, acc, sizeof(acc));
+    if (min_cost) *min_cost = mn;
+    if (max_cost) *max_cost = mx;
+    return UFM_OK;
+}
+int ufm_track_costs(ufm_t *p, int enable) { return p ? engine_track_costs(p->e, enable) : UFM_ERR_INVALID; }
+int ufm_read_cost_census(ufm_t *p, uint64_t hist[256], int *min_cost, int *max_cost) { return p ? census_sum(&p->e, 1, 0, 1, hist, min_cost, max_cost) : UFM_ERR_INVALID; }
+int ufm_heuristic_multiplier(ufm_t *p, float *used) { if (!p || !used) return UFM_ERR_INVALID; *used = p->e->last_multiplier; return UFM_OK; }
 int ufm_set_profiling(ufm_t *p, int enable) { if (!p) return UFM_ERR_INVALID; p->e->profiling = enable != 0; return UFM_OK; }
 void *ufm_stream(ufm_t *p) { return p ? (void *)p->e->stream : nullptr; }
 
@@ -340,6 +364,21 @@ int ufm_batch_set_heuristic_multiplier(ufm_batch_t *b, float mult) {
     for (Engine *e : b->shards) e->heuristic_multiplier = mult;
     return UFM_OK;
 }
+int ufm_batch_track_costs(ufm_batch_t *b, int enable) {
+    if (!b) return UFM_ERR_INVALID;
+    for (Engine *e : b->shards) { const int rc = engine_track_costs(e, enable); if (rc != UFM_OK) return rc; }
+    return UFM_OK;
+}
+int ufm_batch_read_cost_census(ufm_batch_t *b, int i, uint64_t hist[256], int *min_cost, int *max_cost) {
+    if (!b || b->shards.empty() || i < -1 || i >= b->n_maps) return UFM_ERR_INVALID;
+    return i < 0 ? census_sum(b->shards.data(), b->per, 0, b->n_maps, hist, min_cost, max_cost)
+                 : census_sum(b->shards.data(), b->per, i, 1, hist, min_cost, max_cost);
+}
+int ufm_batch_heuristic_multiplier(ufm_batch_t *b, float *used) {
+    if (!b || b->shards.empty() || !used) return UFM_ERR_INVALID;
+    *used = b->shards[0]->last_multiplier;
+    return UFM_OK;
+}
 #define UFM_BATCH_MAP(b, i) Engine *e = nullptr; int li = 0; { const int rc_ = batch_locate(b, i, &e, &li); if (rc_ != UFM_OK) return rc_; }
 int ufm_batch_set_map(ufm_batch_t *b, int i, const uint8_t *host_map, int width, int length) { UFM_BATCH_MAP(b, i); return engine_set_map(e, li, host_map, false, width, length); }
 int ufm_batch_set_map_device(ufm_batch_t *b, int i, const uint8_t *dev_map, int width, int length) { UFM_BATCH_MAP(b, i); return engine_set_map(e, li, dev_map, true, width, length); }
@@ -365,9 +404,24 @@ int ufm_batch_step(ufm_batch_t *b, ufm_stats *stats) {
     const size_t n = b->shards.size();
     std::vector<ufm_stats> st(n);
     std::vector<int> rcs(n, UFM_OK);
+    // "auto_multiplier": one multiplier for the whole batch, the smallest cost over all maps of all shards -- admissible for every map, and
+    // the same however the maps are spread (a shard with a map still missing fails its step below)
+    float auto_mult = 0.0f;
+    const float *auto_ptr = nullptr;
+    if (n > 1 && b->shards[0]->auto_multiplier && b->shards[0]->heur) {
+        int mn = CENSUS_BINS;
+        for (Engine *e : b->shards) {
+            int a = 0, c = 0;
+            if (hipSetDevice(e->device) != hipSuccess) return UFM_ERR_HIP_BASE;
+            const int rc = e->census_minmax(&a, &c);
+            if (rc != UFM_OK) return rc;
+            mn = std::min(mn, a);
+        }
+        auto_mult = (float)mn; auto_ptr = &auto_mult;
+    }
     auto run = [&](size_t s) {
         if (hipSetDevice(b->shards[s]->device) != hipSuccess) { rcs[s] = UFM_ERR_HIP_BASE; return; }
-        rcs[s] = b->shards[s]->step(&st[s]);
+        rcs[s] = b->shards[s]->step(&st[s], auto_ptr);
     };
     if (n == 1) run(0);
     else {

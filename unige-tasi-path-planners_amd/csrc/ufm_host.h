@@ -211,7 +211,7 @@ struct Engine {
     RouteSwitches route_switches() const {
         return RouteSwitches{fuse_control, spin_wait, use_region, use_graph, algo != UFM_ALGO_DFM, region_tiles, region_ahead, P.TX, P.TY, nmaps};
     }
-    int step(ufm_stats *out);
+    int step(ufm_stats *out, const float *auto_mult = nullptr);
     void flush_dyn(StepRun &r);
     int begin_step(StepRun &r);
     void start_elements();
@@ -263,6 +263,22 @@ struct Engine {
     void patch_small(int m, const uint8_t *src, int x, int y, int w, int h) {
         with_elements(algo, [&](auto nodes) { k_patch_small<nodes()><<<1, 1024, 0, stream>>>(P, m, src, d_pmask, x, y, w, h); });
     }
+    // Cost census (ufm_track_costs; ufm_census.h).  Off -- the default -- nothing below exists or runs.  On: d_census
+    // holds, per map, how many cells of P.cost have each value, exactly, between any two calls: built after the raster is final
+    // (engine_set_map), corrected in front of every patch kernel (patch()) -- and the two routes that apply a patch later, the block kernel's
+    // held host patches and a batch's deferred device patches, are declined, as with a footprint.  After every build or patch the smallest
+    // and largest value present are published to h_cen; "auto_multiplier" makes a step take that minimum as its heuristic multiplier.
+    bool census_on = false, auto_multiplier = false;
+    uint32_t *d_census = nullptr;    // [nmaps][256]
+    int *h_cen = nullptr;            // pinned, host-coherent: {min, max} over the engine's maps ...
+    unsigned int *h_cen_flag = nullptr;   // ... and the sequence number of that copy (same allocation)
+    unsigned int cen_seq = 0;
+    float last_multiplier = 1.0f;    // what the last step used (ufm_heuristic_multiplier)
+    void census_build(int m);
+    void census_patch(int m, const uint8_t *dev_patch, int x, int y, int w, int h);
+    void census_publish() { k_census_publish<<<1, CENSUS_BINS, 0, stream>>>(d_census, nmaps, h_cen, h_cen_flag, ++cen_seq); }
+    int census_minmax(int *mn, int *mx);
+    void census_free();
     // step deltas (ufm_track_changes / ufm_read_changes, ufm_delta.h): nothing below exists unless a caller turned tracking on
     bool track = false;
     float *trk_g = nullptr;          // the baseline: the field as the caller was last told, in the layout of P.G (same gstride)
@@ -692,6 +708,7 @@ int Engine::patch_lazy(int m, const uint8_t *host_patch, int x, int y, int w, in
     if (m < 0 || m >= nmaps || !allocated || !maps[m].have_map) return UFM_ERR_INVALID;
     if (x < 0 || y < 0 || w <= 0 || h <= 0 || x + h > L || y + w > W) return UFM_ERR_INVALID;   // Graph.cpp:38-41
     if (cs.on) return UFM_OK;          // (a footprint: the block kernel would apply raw bytes to the planning raster)
+    if (census_on) return UFM_OK;      // (the census: the block kernel would change the raster behind the counters' back)
     if (!(lazy_patches && nmaps == 1 && use_region && fuse_control && spin_wait && w <= 64 && h <= 64)) return UFM_OK;
     if ((int)lazy.size() >= LAZY_SLOTS || pending.size() != lazy.size()) return UFM_OK;      // (only behind other held patches: the block kernel applies them in order)
     if (!h_lazy) HIPCHK(hipHostMalloc(&h_lazy, (size_t)LAZY_SLOTS * 4096, hipHostMallocMapped));
@@ -715,7 +732,7 @@ int Engine::patch(int m, const uint8_t *dev_patch, int x, int y, int w, int h, b
     { int rc = ensure_pmask((size_t)n); if (rc != UFM_OK) return rc; }
     // (a batch only: the patch kernel of a single map runs while the host prepares the step -- applying it inside the
     //  replan's block kernel instead was tried and saved nothing, it only made that kernel longer)
-    if (may_defer && defer_patches && nmaps > 1 && n <= 4096) {
+    if (may_defer && defer_patches && !census_on && nmaps > 1 && n <= 4096) {
         // (one per map at a time: two patches of one map may overlap, and then their order counts)
         bool clash = (int)deferred.size() >= PATCH_MULTI;
         for (const DeferredPatch &d : deferred) clash = clash || d.m == m;
@@ -725,6 +742,7 @@ int Engine::patch(int m, const uint8_t *dev_patch, int x, int y, int w, int h, b
         return UFM_OK;
     }
     { int rc = flush_deferred(); if (rc != UFM_OK) return rc; }   // keep the order of the patches
+    if (census_on) { census_patch(m, dev_patch, x, y, w, h); census_publish(); }   // (reads the old bytes: in front of the kernel that overwrites them)
     if (n <= 4096) {
         patch_small(m, dev_patch, x, y, w, h);
     } else {
@@ -765,6 +783,31 @@ int Engine::patch_raw(int m, const uint8_t *dev_patch, int x, int y, int w, int 
     cspace_dilate(m, d_cs_patch, g.w, g);
     HIPCHK(hipGetLastError());
     return patch(m, d_cs_patch, g.x, g.y, g.w, g.h);
+}
+
+// ---- the cost census: hist[v] == number of cells of P.cost with value v, per map ----
+void Engine::census_build(int m) {
+    uint32_t *hist = d_census + (size_t)m * CENSUS_BINS;
+    (void)hipMemsetAsync(hist, 0, sizeof(uint32_t) * CENSUS_BINS, stream);
+    const CensusBuildJob j{P.cost + (size_t)m * P.cstride, P.cstride, hist};
+    k_census_build<<<census_build_grid(census_split(reinterpret_cast<uintptr_t>(j.cost), j.n).nvec), CENSUS_THREADS, 0, stream>>>(j);
+}
+void Engine::census_patch(int m, const uint8_t *dev_patch, int x, int y, int w, int h) {
+    const CensusPatchJob j{P.cost + (size_t)m * P.cstride, dev_patch, d_census + (size_t)m * CENSUS_BINS, W, x, y, w, h};
+    k_census_patch<<<census_patch_grid(w * h), CENSUS_THREADS, 0, stream>>>(j);
+}
+// the published range as of the last build or patch queued: the host waits for that copy's sequence number (nothing is held while the census is on)
+int Engine::census_minmax(int *mn, int *mx) {
+    if (!census_on) return UFM_ERR_INVALID;
+    { int rc = wait_flag(h_cen_flag, cen_seq); if (rc != UFM_OK) return rc; }
+    *mn = h_cen[0]; *mx = h_cen[1];
+    return UFM_OK;
+}
+void Engine::census_free() {
+    if (d_census) hipFree(d_census);
+    if (h_cen) hipHostFree(h_cen);
+    d_census = nullptr; h_cen = nullptr; h_cen_flag = nullptr;
+    census_on = auto_multiplier = false;
 }
 
 // ---- a step: ReplannerBase::step (ReplannerBase.h:43-75) --------------------------------------------------------------------
@@ -1160,7 +1203,7 @@ void Engine::copy_counters(ufm_stats &st) const {   // the published counter blo
     st.raise_tile_visits = h_ctr->raise_visits;
 }
 
-int Engine::step(ufm_stats *out) {
+int Engine::step(ufm_stats *out, const float *auto_mult) {
     // ReplannerBase.h:44-45
     for (int m = 0; m < nmaps; ++m) if (!maps[m].have_map) return UFM_LOOP_FAILURE_NO_GRAPH;
     for (int m = 0; m < nmaps; ++m) if (!maps[m].goal_set) return UFM_LOOP_FAILURE_NO_GOAL;
@@ -1172,7 +1215,15 @@ int Engine::step(ufm_stats *out) {
     r.plan = plan_step(ROUTE_CONFIG, route_switches(), maps.data(), pending.data(), (int)pending.size(), (int)lazy.size(), r.nr, r.nl,
                        scratch.consume, scratch.init);
     const StepPlan &pl = r.plan;
-    r.dyn_now = DevDyn{heur ? heuristic_multiplier : 0.0f, thr_uchar, focused ? 1 : 0, 0};
+    // "auto_multiplier": the smallest cost of the planning rasters as they stand (a batch: ufm_batch_step hands in the minimum over all shards)
+    // instead of the caller's; it reaches the device like any new multiplier, through the job record or k_set_dyn
+    float mult = heuristic_multiplier;
+    if (auto_multiplier && heur) {
+        if (auto_mult) mult = *auto_mult;
+        else { int mn = 0, mx = 0; const int rc = census_minmax(&mn, &mx); if (rc != UFM_OK) return rc; mult = (float)mn; }
+    }
+    last_multiplier = mult;
+    r.dyn_now = DevDyn{heur ? mult : 0.0f, thr_uchar, focused ? 1 : 0, 0};
     r.dyn_pending = std::memcmp(&r.dyn_now, &dyn_dev, sizeof(DevDyn)) != 0;
     r.band = raise_margin * band_delta(delta_scale);
     { int rc = begin_step(r); if (rc != UFM_OK) return rc; }
@@ -1284,6 +1335,7 @@ int engine_destroy(Engine *e) {
     for (hipEvent_t v : e->own_ev) if (v) hipEventDestroy(v);
     for (hipEvent_t v : e->reg_ev) if (v) hipEventDestroy(v);
     for (hipEvent_t v : e->trk_ev) if (v) hipEventDestroy(v);
+    e->census_free();
     free_all(hipFree, e->d_cs_patch, e->d_patch, e->d_pmask, e->d_field, e->d_info, e->d_jobs, e->d_path);
     free_all(hipHostFree, e->h_jobs, e->h_path, e->h_patch, e->h_lazy);
     e->drop_graphs();
@@ -1303,11 +1355,13 @@ int engine_set_map(Engine *e, int m, const uint8_t *src, bool on_device, int wid
         if (e->allocated && others) return UFM_ERR_INVALID;   // all maps of a batch share one size
         int rc = e->alloc(width, length);
         if (rc != UFM_OK) return rc;
+        if (e->census_on) HIPCHK(hipMemsetAsync(e->d_census, 0, sizeof(uint32_t) * CENSUS_BINS * e->nmaps, e->stream));   // (no map has a raster)
     }
     // (a footprint: the input is the raw raster -- kept, and dilated into the planning raster before anything reads that one)
     HIPCHK(hipMemcpyAsync((e->cs.on ? e->d_raw : e->P.cost) + (size_t)m * e->P.cstride, src, (size_t)width * length,
                           on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, e->stream));
     if (e->cs.on) e->cspace_dilate(m, e->P.cost + (size_t)m * e->P.cstride, width, PatchRect{m, 0, 0, width, length});
+    if (e->census_on) { e->census_build(m); e->census_publish(); }      // (the planning raster is final; published by the wait below)
     k_cost_windows<<<2048, 256, 0, e->stream>>>(e->P, m);
     {   // mean traversable cost -> default ordering band
         unsigned long long *d_acc = reinterpret_cast<unsigned long long *>(e->d_scratch);
@@ -1361,6 +1415,48 @@ int engine_read_raw_map(Engine *e, int m, uint8_t *host_map) {
     if (!e || !host_map || !e->cs.on || !e->allocated || m < 0 || m >= e->nmaps || !e->maps[m].have_map) return UFM_ERR_INVALID;
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipMemcpyAsync(host_map, e->d_raw + (size_t)m * e->P.cstride, e->P.cstride, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return UFM_OK;
+}
+
+// ufm_track_costs / ufm_batch_track_costs.  On, with maps already set: what is held is applied and the counters are built from the rasters
+// as they stand.  Off frees everything; refused while "auto_multiplier" is 1 (the step would have nothing to take).
+int engine_track_costs(Engine *e, int enable) {
+    if (!e) return UFM_ERR_INVALID;
+    HIPCHK(hipSetDevice(e->device));
+    if (!enable) {
+        if (!e->census_on) return UFM_OK;
+        if (e->auto_multiplier) return UFM_ERR_INVALID;
+        HIPCHK(hipStreamSynchronize(e->stream));
+        e->census_free();
+        return UFM_OK;
+    }
+    if (e->census_on) return UFM_OK;
+    if (e->allocated) { int rc = e->flush_deferred(); if (rc != UFM_OK) return rc; }
+    const int rc = [&]() -> int {
+        HIPCHK(hipMalloc(&e->d_census, sizeof(uint32_t) * CENSUS_BINS * e->nmaps));
+        void *pub = nullptr;
+        HIPCHK(hipHostMalloc(&pub, 128, hipHostMallocMapped | hipHostMallocCoherent));
+        std::memset(pub, 0, 128);
+        e->h_cen = static_cast<int *>(pub);
+        e->h_cen_flag = reinterpret_cast<unsigned int *>(static_cast<char *>(pub) + 64);
+        e->cen_seq = 0;
+        HIPCHK(hipMemsetAsync(e->d_census, 0, sizeof(uint32_t) * CENSUS_BINS * e->nmaps, e->stream));
+        for (int m = 0; m < e->nmaps; ++m) if (e->allocated && e->maps[m].have_map) e->census_build(m);
+        e->census_publish();
+        HIPCHK(hipGetLastError());
+        return UFM_OK;
+    }();
+    if (rc != UFM_OK) { (void)hipStreamSynchronize(e->stream); e->census_free(); return rc; }
+    e->census_on = true;
+    return UFM_OK;
+}
+// the counters of map m, as they are once everything queued has run
+int engine_read_census(Engine *e, int m, uint32_t out[CENSUS_BINS]) {
+    if (!e || !e->census_on || !e->allocated || m < 0 || m >= e->nmaps || !e->maps[m].have_map) return UFM_ERR_INVALID;
+    HIPCHK(hipSetDevice(e->device));
+    { int rc = e->flush_deferred(); if (rc != UFM_OK) return rc; }
+    HIPCHK(hipMemcpyAsync(out, e->d_census + (size_t)m * CENSUS_BINS, sizeof(uint32_t) * CENSUS_BINS, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     return UFM_OK;
 }

@@ -166,7 +166,7 @@ class Pipes:
 
 def run_mission(cmd, pipe_to_planner, pipe_from_planner, img_h, start, goal, radius=5, cspace_diameter=1,
                 low_res_penalty=10, use_heuristic=False, max_moves=10000, on_map=None, on_move=None, display_shift=0.0,
-                append_pipes=True, tof=False, on_expanded=None, planner_inflates=False):
+                append_pipes=True, tof=False, on_expanded=None, planner_inflates=False, planner_min_cost=False):
     """One mission as Tests/run_test.py:85-177 runs it: launch the planner process `cmd`, send the
     C-space of the low-resolution map, then per robot position reveal the disc of radius `radius`,
     send its bounding patch and the heuristic hint, receive the planned path.  start / goal are
@@ -177,7 +177,9 @@ def run_mission(cmd, pipe_to_planner, pipe_from_planner, img_h, start, goal, rad
     (position without `display_shift`, the half cell the DFM driver adds for display); with tof the planner is asked for its dump of the
     expanded elements after every step and on_expanded(i, records) gets it (Pipes.receive_expanded).
     planner_inflates: the planner process dilates on its own (ufm_planner --inflate D with D = cspace_diameter): the low-resolution map and
-    the patches are sent RAW, and on_map / on_move get what was sent; min_cost is still taken from the inflated map.  Returns the list of positions visited and whether the planner reported the end."""
+    the patches are sent RAW, and on_map / on_move get what was sent; min_cost is still taken from the inflated map.
+    planner_min_cost: the planner process finds the heuristic multiplier itself (ufm_planner --auto-heuristic): the hint on the wire is a
+    placeholder, int(data_l.min()) -- and together with planner_inflates nothing is dilated here at all.  Returns the list of positions visited and whether the planner reported the end."""
     for p in (pipe_to_planner, pipe_from_planner):
         if not os.path.exists(p):
             os.mkfifo(p)
@@ -191,8 +193,9 @@ def run_mission(cmd, pipe_to_planner, pipe_from_planner, img_h, start, goal, rad
         assert io.recv("b") == (0,)
         io.send("b", 0)
         data_l, data_h = simulation_data(img_h, low_res_penalty)
-        cspace = dilate(data_l, cspace_diameter)
-        min_cost = int(cspace.min())
+        host_inflates = not (planner_inflates and planner_min_cost)
+        cspace = dilate(data_l, cspace_diameter) if host_inflates else data_l
+        min_cost = int(data_l.min()) if planner_min_cost else int(cspace.min())
         height, width = cspace.shape
         io.send("ii", width, height)
         io.send_bytes(np.ascontiguousarray(data_l if planner_inflates else cspace).tobytes())
@@ -217,10 +220,10 @@ def run_mission(cmd, pipe_to_planner, pipe_from_planner, img_h, start, goal, rad
             trace.append((x, y))
             center = (int(round(yr)), int(round(xr)))         # (col, row) of the position as received, run_test.py:143
             data_l, (top, left), ranges = round_patch_update(data_l, data_h, center, radius)
-            cspace = dilate(data_l, cspace_diameter)
+            cspace = dilate(data_l, cspace_diameter) if host_inflates else data_l
             patch = np.ascontiguousarray((data_l if planner_inflates else cspace)[ranges[0], ranges[1]])
             if use_heuristic:
-                min_cost = int(cspace.min())
+                min_cost = int(data_l.min()) if planner_min_cost else int(cspace.min())
             io.send("b", 1)
             io.send("iiii", top, left, patch.shape[0], patch.shape[1])
             io.send_bytes(patch.tobytes())

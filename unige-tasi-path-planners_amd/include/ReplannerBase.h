@@ -53,6 +53,7 @@ class ReplannerBase {
       const int rd = map.apply_changes();
       if (rd != UFM_OK) { last_error = rd; return rd; }
     }
+    if (auto_heuristic_) check(ufm_heuristic_multiplier(handle_, &used_multiplier_));   // the queue view's keys use what the step used
     u_time = st.u_ms; p_time = st.p_ms;
     num_nodes_updated = st.updated; num_nodes_expanded = st.expanded;
     stats = st;
@@ -68,6 +69,28 @@ class ReplannerBase {
    *  RAW raster; `grid` keeps holding that raw raster, the engine plans (and the extractor walks) on its dilation. */
   void set_cspace(const uint8_t *mask, int mw, int mh, int anchor_row = -1, int anchor_col = -1) {
     check(ufm_set_cspace(handle_, mask, mw, mh, anchor_row, anchor_col));
+  }
+  /** Cost census (ufm_track_costs; no reference counterpart: the reference's simulator takes cv2.minMaxLoc of the map it inflated itself,
+   *  run_simulator.py:152,183): exact counts of the PLANNING raster's values, kept under patches.  min_cost(): the smallest value present,
+   *  -1 if the census is off or no map is set; cost_census(): all 256 counters, returns the ufm code. */
+  void track_costs(bool on = true) { check(ufm_track_costs(handle_, on ? 1 : 0)); }
+  int min_cost() {
+    int mn = -1;
+    const int rc = ufm_read_cost_census(handle_, nullptr, &mn, nullptr);
+    if (rc != UFM_OK) { last_error = rc; return -1; }
+    return mn;
+  }
+  int cost_census(uint64_t hist[256], int *min_cost = nullptr, int *max_cost = nullptr) {
+    const int rc = ufm_read_cost_census(handle_, hist, min_cost, max_cost);
+    if (rc != UFM_OK) last_error = rc;
+    return rc;
+  }
+  /** step() takes min_cost() of the planning raster as it stands as the heuristic multiplier, as the reference's drivers do with the
+   *  simulator's hint (DFM/main.cpp:111-112); set_heuristic_multiplier is stored and ignored meanwhile.  Turns the census on. */
+  void set_auto_heuristic(bool on = true) {
+    check(ufm_set_param(handle_, "auto_multiplier", on ? 1.0 : 0.0));
+    auto_heuristic_ = on;
+    used_multiplier_ = heuristic_multiplier;
   }
   void set_map(const std::shared_ptr<uint8_t> &new_map, int w, int h) {
     grid.init(new_map, w, h);
@@ -129,7 +152,7 @@ class ReplannerBase {
       float dist;
       if constexpr (std::is_same<MapElem_, Node>::value) dist = s.distance(grid.start_pos_);
       else dist = grid.start_cell_.distance(s);
-      return {cost_so_far + heuristic_multiplier * dist, cost_so_far};
+      return {cost_so_far + (auto_heuristic_ ? used_multiplier_ : heuristic_multiplier) * dist, cost_so_far};
     }
   }
   ~ReplannerBase() { if (handle_) ufm_destroy(handle_); }
@@ -139,6 +162,8 @@ class ReplannerBase {
  private:
   void check(int rc) { if (rc != UFM_OK) last_error = rc; }
   ufm_t *handle_ = nullptr;
+  bool auto_heuristic_ = false;
+  float used_multiplier_ = 1;
 };
 
 namespace ufm_detail {
