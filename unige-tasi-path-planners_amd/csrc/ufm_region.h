@@ -674,33 +674,6 @@ __global__ __launch_bounds__(NTHR) void k_replan_region(DevParams P, RegionJobs 
         __syncthreads();
     }
 
-    // ---- 2b. the back-pointers (what k_finalize_bp does for the launch chain's steps): every node of a patch in which a value changed, and of
-    // the patches around it -- a neighbour's value may be what it was and still come from another triangle now --, evaluated once more on the
-    // values as they stand, the arg-min kept.  (MS-DFM level 0 has none.)
-    {
-        const int w = wave_index16(tid >> 6), lane = tid & 63, q = lane & 3, nd = lane >> 2;
-        const int nprow = J.ntx * TP, npcol = J.nty * TP;
-        auto cost_at = [=](int r, int c) { const int b = Cb[r * RCP + c]; return b >= thr ? INFINITY : (float)b; };
-        for (int wd = 0; wd < RWW; ++wd) {
-            int bits = __builtin_amdgcn_readfirstlane(S.renew[w][wd]);
-            while (bits) {
-                const int j = __ffs(bits) - 1;
-                bits &= bits - 1;
-                const int idx = wd * 32 + j;
-                const int pr = (idx / RPW) * 4 + (w >> 2), pc = (idx % RPW) * 4 + (w & 3);
-                if (pr >= nprow || pc >= npcol) continue;
-                const int lx = pr * 4 + (nd >> 2), ly = pc * 4 + (nd & 3);
-                QuadConsts<ALGO> C;
-                C.load_at(cost_at, lx, ly, q, RP);
-                const LaneEval le = eval_quad_w<ALGO, RP>(Gs + (lx + 1) * RP + ly + 1, q, C);
-                const float nv = quad_min(le.r);
-                const int bq = quad_min_int(bp_byte<ALGO>(le, q, C, le.r == nv)), b = bp_of_key<ALGO>(bq);
-                if (q == 0) Bb[lx * RBP + ly] = (uint8_t)((lx == goal_lx && ly == goal_ly) ? BP_NONE : b);
-                if (lane == 0) S.tbp[(pr / TP) * J.nty + pc / TP] = 1;
-            }
-        }
-        __syncthreads();
-    }
     if (tid == 0) S.tstamp[4] = wall_clock64();
     // ---- 3. write back: changed values, the rings of the neighbours they border, what the frame has to hear ----
     // frame tile index of the tile at block coordinates (ti, tj), ti in -1..ntx, tj in -1..nty (one of them outside)
@@ -717,7 +690,7 @@ __global__ __launch_bounds__(NTHR) void k_replan_region(DevParams P, RegionJobs 
     constexpr int UPT = TT / 64;                                        // units (64 consecutive elements = one wave) per tile
     const int wvw = __builtin_amdgcn_readfirstlane(tid >> 6), lnw = tid & 63;
     if (tid < 64) {
-        const bool has = tid < ntl && (S.tflag[tid] | S.tbp[tid]);
+        const bool has = tid < ntl && S.tflag[tid];      // (the tiles that only hold renewed back-pointers: the tail's list, behind the flag)
         const unsigned long long hm_ = __builtin_amdgcn_ballot_w64(has);
         if (has) s_wbl[__popcll(hm_ & ((1ull << tid) - 1ull))] = tid;
         if (tid == 0) s_nwb = __popcll(hm_);
@@ -735,7 +708,7 @@ __global__ __launch_bounds__(NTHR) void k_replan_region(DevParams P, RegionJobs 
         for (int u = wvw; u < nunits; u += 16) {
             int k, part, tl, ti, tj;
             unit_tile(u, k, part, tl, ti, tj);
-            if (!S.tflag[tl] || k >= NG0) continue;
+            if (k >= NG0) continue;
             const size_t gt = (size_t)(gt0 + (J.tx0 + ti) * P.TY + J.ty0 + tj);
             __builtin_amdgcn_global_load_lds((glb_ptr)(P.G + gt * TT + part * 64 + lnw), (lds_ptr)(G0c + k * TT + part * 64), 4, 0, 0);
         }
@@ -748,9 +721,6 @@ __global__ __launch_bounds__(NTHR) void k_replan_region(DevParams P, RegionJobs 
         int k, part, tl, ti, tj;
         unit_tile(u, k, part, tl, ti, tj);
         const int e = part * 64 + lnw;
-        // the renewed back-pointers of the tile (a patch next to a changed one may lie in an unchanged tile)
-        if (S.tbp[tl]) P.bp[(size_t)(gt0 + (J.tx0 + ti) * P.TY + J.ty0 + tj) * TT + e] = Bb[(ti * T + e / T) * RBP + tj * T + e % T];
-        if (!S.tflag[tl]) continue;                                         // nothing was applied in this tile
         const int tx = J.tx0 + ti, ty = J.ty0 + tj, gt = gt0 + tx * P.TY + ty;
         const int io_r = e / T, io_c = e % T;
         float gl0;
@@ -918,6 +888,7 @@ __global__ __launch_bounds__(NTHR) void k_replan_region(DevParams P, RegionJobs 
                 for (int i = 0; i < 8; ++i) d[22 + i] = S.dbg[i];
                 S.tstamp[6] = wall_clock64();
                 for (int i = 1; i < 7; ++i) d[30 + i] = (int)(S.tstamp[i] - S.tstamp[0]);
+                d[37] = 0; d[38] = 0;      // (flag at / kernel end at: stamped below)
                 for (int i = 1; i < 8; ++i) d[40 + i] = (int)(s_tb[i] - s_tb[0]);
                 for (int i = 0; i < 16; ++i) d[50 + i] = s_simd[i];
                 for (int i = 0; i < 8; ++i) d[70 + i] = S.dbg2[i];
@@ -932,7 +903,6 @@ __global__ __launch_bounds__(NTHR) void k_replan_region(DevParams P, RegionJobs 
         for (int u = wvw; u < nunits; u += 16) {
             int k, part, tl, ti, tj;
             unit_tile(u, k, part, tl, ti, tj);
-            if (!S.tflag[tl]) continue;
             const int e = part * 64 + lnw;
             const int gt = gt0 + (J.tx0 + ti) * P.TY + J.ty0 + tj;
             if (k < NG0) P.Gprev[(size_t)gt * TT + e] = G0c[k * TT + e];
@@ -944,25 +914,88 @@ __global__ __launch_bounds__(NTHR) void k_replan_region(DevParams P, RegionJobs 
     }
     if (J.batch) __threadfence();          // (a single map: the kernel's end, or thread 0's system-scope release below, publishes)
     __syncthreads();
-    if (J.batch) {             // the last workgroup to get here publishes for all of them
+    // ---- 5. publish.  Everything the host reads (the counters) and everything it may follow up on without a kernel of this stream in between
+    // is in place; what is left -- the back-pointer bytes -- has no reader that is not ordered behind this kernel on the engine's stream:
+    // the next k_replan_region's staging, k_relax's invalidation, k_finalize_bp, k_info_stored and the check-info kernel, the delta scan, the
+    // path kernels and the hipMemsetAsync of a re-initialisation are all submitted to it, the engine has no second stream, and the calls that
+    // free or regrow device memory synchronise it first.  So the host leaves step() here and prepares the next call while the tail runs (as
+    // finalize_bp(1) behind k_replan_end's publication does for the launch chain's steps, fused_end()).  The tail writes P.bp -- and, with the
+    // diagnostics on, its time stamp -- and nothing else: not `host`, not `flag`, no field of P.ctr.
+    if (J.batch) {             // the last workgroup to get here publishes for all of them; the others go on to their tails
         if (tid == 0) s_last = (atomicAdd(&P.ctr->fin_blocks, 1) == (int)gridDim.x - 1);
         __syncthreads();
-        if (!s_last) return;
-        __threadfence();
-        if (tid == 0) {
-            P.ctr->fin_blocks = 0;
-            P.ctr->scount = 0;
-            P.ctr->done = __hip_atomic_load(&P.ctr->done_fail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0 ? 1 : 0;
+        if (s_last) {
+            __threadfence();
+            if (tid == 0) {
+                P.ctr->fin_blocks = 0;
+                P.ctr->scount = 0;
+                P.ctr->done = __hip_atomic_load(&P.ctr->done_fail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0 ? 1 : 0;
+            }
+            __threadfence();
+            __syncthreads();
         }
-        __threadfence();
+    }
+    if (!J.batch || s_last) {
+        const int *src = reinterpret_cast<const int *>(P.ctr);
+        int *dst = reinterpret_cast<int *>(host);
+        for (int i = tid; i < (int)(sizeof(DevCounters) / sizeof(int)); i += NTHR)
+            dst[i] = __hip_atomic_load(&src[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        // (no fence of every wave's own here: the barrier orders the copies before thread 0's store, whose system-scope release writes
+        //  the L2 back once)
+        __syncthreads();
+        if (tid == 0) {
+            if (J.debug & 2) P.lmax[37] = (int)(wall_clock64() - S.tstamp[0]);
+            __hip_atomic_store(flag, J.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
+
+    // ---- 6. the tail, behind the flag: the back-pointers (what k_finalize_bp does for the launch chain's steps).  Every node of a patch in
+    // which a value changed, and of the patches around it -- a neighbour's value may be what it was and still come from another triangle
+    // now --, is evaluated once more on the values as they stand, the arg-min kept.  (MS-DFM level 0 has none.)
+    {
+        const int w = wave_index16(tid >> 6), lane = tid & 63, q = lane & 3, nd = lane >> 2;
+        const int nprow = J.ntx * TP, npcol = J.nty * TP;
+        auto cost_at = [=](int r, int c) { const int b = Cb[r * RCP + c]; return b >= thr ? INFINITY : (float)b; };
+        for (int wd = 0; wd < RWW; ++wd) {
+            int bits = __builtin_amdgcn_readfirstlane(S.renew[w][wd]);
+            while (bits) {
+                const int j = __ffs(bits) - 1;
+                bits &= bits - 1;
+                const int idx = wd * 32 + j;
+                const int pr = (idx / RPW) * 4 + (w >> 2), pc = (idx % RPW) * 4 + (w & 3);
+                if (pr >= nprow || pc >= npcol) continue;
+                const int lx = pr * 4 + (nd >> 2), ly = pc * 4 + (nd & 3);
+                QuadConsts<ALGO> C;
+                C.load_at(cost_at, lx, ly, q, RP);
+                const LaneEval le = eval_quad_w<ALGO, RP>(Gs + (lx + 1) * RP + ly + 1, q, C);
+                const float nv = quad_min(le.r);
+                const int bq = quad_min_int(bp_byte<ALGO>(le, q, C, le.r == nv)), b = bp_of_key<ALGO>(bq);
+                if (q == 0) Bb[lx * RBP + ly] = (uint8_t)((lx == goal_lx && ly == goal_ly) ? BP_NONE : b);
+                if (lane == 0) S.tbp[(pr / TP) * J.nty + pc / TP] = 1;
+            }
+        }
         __syncthreads();
     }
-    const int *src = reinterpret_cast<const int *>(P.ctr);
-    int *dst = reinterpret_cast<int *>(host);
-    for (int i = tid; i < (int)(sizeof(DevCounters) / sizeof(int)); i += NTHR)
-        dst[i] = __hip_atomic_load(&src[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    // (no fence of every wave's own here: the barrier orders the copies before thread 0's store, whose system-scope release writes
-    //  the L2 back once)
+    // the renewed bytes of the tiles that hold some (a patch next to a changed one may lie in an unchanged tile): a list of their own
+    if (tid < 64) {
+        const bool has = tid < ntl && S.tbp[tid];
+        const unsigned long long hm_ = __builtin_amdgcn_ballot_w64(has);
+        if (has) s_wbl[__popcll(hm_ & ((1ull << tid) - 1ull))] = tid;
+        if (tid == 0) s_nwb = __popcll(hm_);
+    }
     __syncthreads();
-    if (tid == 0) __hip_atomic_store(flag, J.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    const int nunits_bp = s_nwb * UPT;
+#pragma unroll 1
+    for (int u = wvw; u < nunits_bp; u += 16) {
+        int k, part, tl, ti, tj;
+        unit_tile(u, k, part, tl, ti, tj);
+        const int e = part * 64 + lnw;
+        P.bp[(size_t)(gt0 + (J.tx0 + ti) * P.TY + J.ty0 + tj) * TT + e] = Bb[(ti * T + e / T) * RBP + tj * T + e % T];
+    }
+    // diagnostics: the kernel's end (read behind a stream synchronisation: ufm_debug_lmax).  A batch: every workgroup stamps the same word, the
+    // last writer stays -- the end of some workgroup's tail, next to the publisher's "flag at"
+    if (J.debug & 2) {
+        __syncthreads();
+        if (tid == 0) P.lmax[38] = (int)(wall_clock64() - S.tstamp[0]);
+    }
 }
