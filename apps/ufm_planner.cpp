@@ -12,7 +12,7 @@
 // LinearInterpolationPathExtractor, reset / set_* / patch_map / step / extract_path, u_time,
 // p_time, e_time, map.size(), map.buckets.
 //
-//   ufm_planner [--planner FD|SG|DFM] [--level K] [--max-moves N] [--verify-follow] [--inflate D] [--auto-heuristic] <fifo_in> <fifo_out>
+//   ufm_planner [--planner FD|SG|DFM] [--level K] [--max-moves N] [--verify-follow] [--inflate D] [--auto-heuristic] [--sense R] <fifo_in> <fifo_out>
 //        start, goal and the `tof` flag arrive in-band after the map (DFM/main.cpp:62-67)
 //   ufm_planner [...] <mapfile> <from_x> <from_y> <to_x> <to_y> <cspace> <fifo_in> <fifo_out> <gui> <tof> <outpath>
 //        the 11-argument form of FDSTAR/main.cpp:16-31 and SGDFM/main.cpp
@@ -22,12 +22,18 @@
 // --auto-heuristic: the heuristic multiplier is the smallest cost of the planning raster as the engine holds it (the cost census,
 // ufm_track_costs + "auto_multiplier"); the wire's min_cost is read, as the protocol demands, and not used -- with --inflate the simulator
 // then need not know the inflated map at all.
+// --sense R: the planner senses for itself (ufm_set_sensor / ufm_set_survey / ufm_reveal).  The survey raster -- the simulator's
+// high-resolution data, of the map's size -- arrives ONCE, directly after the map raster; every move's patch message then has h = w = 0
+// and no bytes, and before each step the planner uncovers the disc x^2 + y^2 <= R^2 around the cell it has just reported: each
+// coordinate AS SENT (the cell planners' display shift included) rounded half-to-even, as Python's round does at Tests/run_test.py:143.
+// Composes with --inflate and --auto-heuristic: the simulator then touches no raster after the start.
 // With `tof` the expanded-element dump after every step is kept up to date from the steps' deltas (ExpandedMap::follow_changes), not
 // read back whole; --verify-follow also builds it the old way every step -- a read of the whole field through a second view of the
 // same planner -- and ends the run (exit code 3) if the two differ in any element, value, Info or order.
 // Keys with the heuristic term unless compiled with -DNO_HEURISTIC (binary ufm_planner_no_heur),
 // as for the reference's *_no_heur targets.
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -80,6 +86,7 @@ struct Options {
   bool verify_follow = false;
   int inflate = 0;           // --inflate D: footprint diameter (<= 1: off)
   bool auto_heuristic = false;   // --auto-heuristic: the multiplier follows the engine's planning raster
+  int sense = -1;            // --sense R: radius of the field of view the planner uncovers itself (< 0: off)
   std::string fifo_in, fifo_out;
 };
 
@@ -98,6 +105,11 @@ int serve(Options opt, bool cell_planner, bool indirect) {
   if (width <= 0 || height <= 0) throw std::runtime_error("bad map size");
   auto data = byte_block((size_t)width * height);
   io.get_bytes(data.get(), (size_t)width * height);
+  std::shared_ptr<uint8_t> survey;
+  if (opt.sense >= 0) {
+    survey = byte_block((size_t)width * height);
+    io.get_bytes(survey.get(), (size_t)width * height);
+  }
   if (opt.inband) {
     opt.from_x = io.get<float>(); opt.from_y = io.get<float>();
     opt.to_x = io.get<float>(); opt.to_y = io.get<float>();
@@ -125,6 +137,29 @@ int serve(Options opt, bool cell_planner, bool indirect) {
     planner.set_cspace(disc.data(), n, n);
   }
   planner.set_map(data, width, height);
+  // --sense: the disc of harness.round_patch_update / run_simulator.py:9-28.  A position on the map's far border rounds to a cell one
+  // beyond the last (nodes run 0 .. length): the simulator's disc then hangs over the border, here the anchor moves by that one cell.
+  std::vector<uint8_t> fov;
+  int fov_n = 0, fov_ar = -1, fov_ac = -1;
+  auto sense_at = [&](float sent_x, float sent_y) {
+    const int r = opt.sense;
+    int row = (int)std::nearbyint(sent_x), col = (int)std::nearbyint(sent_y);
+    const int crow = std::min(std::max(row, 0), height - 1), ccol = std::min(std::max(col, 0), width - 1);
+    const int ar = r + crow - row, ac = r + ccol - col;
+    if (ar < 0 || ac < 0 || ar >= fov_n || ac >= fov_n) return;        // (the whole disc lies outside the map: nothing is seen)
+    if (ar != fov_ar || ac != fov_ac) { planner.set_sensor(fov.data(), fov_n, fov_n, ar, ac); fov_ar = ar; fov_ac = ac; }
+    if (planner.reveal(crow, ccol) != UFM_OK) throw std::runtime_error("reveal failed with " + std::to_string(planner.last_error));
+  };
+  if (opt.sense >= 0) {
+    const int r = opt.sense;
+    fov_n = 2 * r + 1;
+    if (fov_n > 127) throw std::runtime_error("--sense: the field of view is at most 127 cells wide");
+    fov.resize((size_t)fov_n * fov_n);
+    for (int a = 0; a < fov_n; ++a)
+      for (int b = 0; b < fov_n; ++b) fov[(size_t)a * fov_n + b] = (a - r) * (a - r) + (b - r) * (b - r) <= r * r;
+    planner.set_survey(survey, width, height);
+    if (planner.last_error != UFM_OK) throw std::runtime_error("set_survey failed with " + std::to_string(planner.last_error));
+  }
   // the dump after every step: follow the steps' deltas on the host instead of reading the whole field back each time
   if (opt.tof && planner.map.follow_changes(true) != UFM_OK) throw std::runtime_error("follow_changes failed");
   planner.set_start(next_point);
@@ -146,6 +181,7 @@ int serve(Options opt, bool cell_planner, bool indirect) {
     auto patch = byte_block((size_t)pw * ph + 1);
     io.get_bytes(patch.get(), (size_t)pw * ph);
     if (pw > 0 && ph > 0) planner.patch_map(patch, top, left, pw, ph);
+    if (opt.sense >= 0) sense_at(next_point.x + shift, next_point.y + shift);
     min_cost = io.get<int32_t>();
     if (!opt.auto_heuristic) planner.set_heuristic_multiplier((float)min_cost);
 
@@ -203,7 +239,7 @@ int serve(Options opt, bool cell_planner, bool indirect) {
 
 void usage(const char *argv0) {
   std::fprintf(stderr,
-               "Usage:\n\t%s [--planner FD|SG|DFM] [--level K] [--max-moves N] [--verify-follow] [--inflate D] [--auto-heuristic] <fifo_in> <fifo_out>\n"
+               "Usage:\n\t%s [--planner FD|SG|DFM] [--level K] [--max-moves N] [--verify-follow] [--inflate D] [--auto-heuristic] [--sense R] <fifo_in> <fifo_out>\n"
                "\t%s [...] <mapfile> <from_x> <from_y> <to_x> <to_y> <cspace> <fifo_in> <fifo_out> <gui> <tof> <outpath>\n",
                argv0, argv0);
 }
@@ -235,6 +271,7 @@ int main(int argc, char **argv) {
     else if (a == "--verify-follow") opt.verify_follow = true;
     else if (a == "--inflate" && i + 1 < argc) opt.inflate = std::atoi(argv[++i]);
     else if (a == "--auto-heuristic") opt.auto_heuristic = true;
+    else if (a == "--sense" && i + 1 < argc) opt.sense = std::atoi(argv[++i]);
     else if (a == "-h" || a == "--help") { usage(argv[0]); return 0; }
     else pos.push_back(a);
   }

@@ -307,6 +307,36 @@ int ufm_track_costs(ufm_t *p, int enable);
 int ufm_read_cost_census(ufm_t *p, uint64_t hist[256], int *min_cost, int *max_cost);
 int ufm_heuristic_multiplier(ufm_t *p, float *used);
 
+/* ---- sensor reveal: a move uncovers the survey raster in HBM.  One raster operation of the reference's per-move loop is left on the host
+ * once ufm_set_cspace and ufm_track_costs are in use: round_patch_update (Simulator/simulator/run_simulator.py:9-28,177, Tests/run_test.py:143)
+ * keeps the high-resolution raster, copies its disc around the robot into the low-resolution one, cuts the bounding rectangle and ships
+ * it.  Here the high-resolution raster -- the SURVEY, what the sensor would see -- lies in device memory next to the map, and a move is
+ * one call with a position.  OPT-IN: with no sensor and no survey set nothing is allocated, nothing is launched, no route changes.
+ * ufm_set_sensor: the field of view is DATA, not a radius, exactly as the footprint of ufm_set_cspace is -- mask[mh][mw], row-major uint8,
+ * non-zero = seen, with an anchor (anchor_row, anchor_col); -1, -1: (mh / 2, mw / 2).  1 <= mw, mh <= 127, the anchor inside the mask, at
+ * least one cell set (the anchor cell need not be).  It may be set or replaced between any two calls and needs no map.
+ * ufm_set_survey / ufm_set_survey_device: one raster per map, [length][width] uint8, copied to device memory at the call.  The map must
+ * already have a raster of exactly these dimensions.  A later ufm_set_map* keeps the survey if the dimensions are unchanged and drops it
+ * otherwise; ufm_reset leaves it alone.  ufm_read_survey copies it back (UFM_ERR_INVALID with no survey set).
+ * ufm_reveal(p, row, col, changed), defined by equivalence.  Let R be the mask's bounding rectangle placed with its anchor on cell
+ * (row, col) and clipped to the map on all four sides; the mask is NOT reflected: mask cell (a, b) covers map cell
+ * (row + a - anchor_row, col + b - anchor_col).  Let Q[i][j] = survey[i][j] where the mask covers (i, j), and elsewhere the caller's raster
+ * as it stands -- the RAW raster if a footprint is set, the planning raster otherwise.  The call then leaves the handle in exactly the
+ * state ufm_patch_map_device(p, Q, R.x, R.y, R.w, R.h) would: the raw store, planning == dilate(raw), the census, the pending
+ * rectangles, ufm_stats::updated / expanded of the next step, step deltas.  Patches that are being held (a single planner's small host
+ * patches, a batch's "defer_patches") are applied first, in order.  Q is made on the device by one launch whose work is proportional to
+ * R, never to the map.
+ * changed: the number of cells of the caller's raster whose byte changed.  Non-NULL makes the call wait for the stream; NULL queues the
+ * call and returns.  A reveal that changes nothing is a patch that changes nothing.
+ * UFM_ERR_INVALID, before anything is launched or written, the handle staying usable: a NULL handle or mask, sizes out of range, an
+ * anchor outside the mask, a mask with no cell set; survey dimensions that differ from the map's, or a survey for a map without a
+ * raster; a reveal with no sensor, no survey or no map; a centre outside [0, length) x [0, width). ---- */
+int ufm_set_sensor(ufm_t *p, const uint8_t *mask, int mw, int mh, int anchor_row, int anchor_col);
+int ufm_set_survey(ufm_t *p, const uint8_t *host_survey, int width, int length);
+int ufm_set_survey_device(ufm_t *p, const uint8_t *dev_survey, int width, int length);
+int ufm_reveal(ufm_t *p, int row, int col, uint64_t *changed);
+int ufm_read_survey(ufm_t *p, uint8_t *host_survey);
+
 /* ---- measurement hooks ---- */
 int ufm_set_profiling(ufm_t *p, int enable);   /* HIP-event timing of every relax launch */
 void *ufm_stream(ufm_t *p);                    /* hipStream_t the kernels run on */
@@ -364,6 +394,19 @@ int ufm_batch_read_raw_map(ufm_batch_t *b, int i, uint8_t *host_map);
 int ufm_batch_track_costs(ufm_batch_t *b, int enable);
 int ufm_batch_read_cost_census(ufm_batch_t *b, int i, uint64_t hist[256], int *min_cost, int *max_cost);
 int ufm_batch_heuristic_multiplier(ufm_batch_t *b, float *used);
+/* as ufm_set_sensor / ufm_set_survey* / ufm_reveal / ufm_read_survey: one field of view for every map on every shard, a survey per map
+ * (UFM_ERR_INVALID for an index outside the batch).  ufm_batch_reveal: every engine runs ONE reveal launch for all its maps (a sharded
+ * handle groups the maps by device) into per-map slots of a patch buffer the engine owns; each map's slot then takes the route its
+ * ufm_batch_patch_map_device would, "defer_patches" included -- the buffer being the engine's, that option's lifetime caveat does not
+ * arise: what is held and points into it is applied before the next reveal writes it.  centres: [n_maps][2] = (row, col), a map with
+ * row < 0 is skipped (untouched, changed = 0); changed: [n_maps] or NULL, as ufm_reveal's.  Every map is checked before anything is
+ * launched on any shard. */
+int ufm_batch_set_sensor(ufm_batch_t *b, const uint8_t *mask, int mw, int mh, int anchor_row, int anchor_col);
+int ufm_batch_set_survey(ufm_batch_t *b, int i, const uint8_t *host_survey, int width, int length);
+int ufm_batch_set_survey_device(ufm_batch_t *b, int i, const uint8_t *dev_survey, int width, int length);
+int ufm_batch_reveal(ufm_batch_t *b, const int32_t *centres /* [n_maps][2] = (row, col); row < 0: this map is skipped */,
+                     uint64_t *changed /* [n_maps] or NULL */);
+int ufm_batch_read_survey(ufm_batch_t *b, int i, uint8_t *host_survey);
 /* all maps in one launch: path_xy [n_maps][cap_points][2], step_costs [n_maps][cap_costs], info [n_maps] */
 int ufm_batch_extract_path(ufm_batch_t *b, int max_steps, int lookahead, int allow_indirect,
                            float *path_xy, int cap_points, float *step_costs, int cap_costs, ufm_path_info *info);

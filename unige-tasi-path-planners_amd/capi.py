@@ -29,6 +29,8 @@ SYMBOLS = [
     "ufm_set_cspace", "ufm_read_raw_map", "ufm_batch_set_cspace", "ufm_batch_read_raw_map",
     "ufm_track_costs", "ufm_read_cost_census", "ufm_heuristic_multiplier",
     "ufm_batch_track_costs", "ufm_batch_read_cost_census", "ufm_batch_heuristic_multiplier",
+    "ufm_set_sensor", "ufm_set_survey", "ufm_set_survey_device", "ufm_reveal", "ufm_read_survey",
+    "ufm_batch_set_sensor", "ufm_batch_set_survey", "ufm_batch_set_survey_device", "ufm_batch_reveal", "ufm_batch_read_survey",
 ]
 
 
@@ -173,6 +175,16 @@ def load_library():
     L.ufm_batch_track_costs.argtypes = [vp, i]
     L.ufm_batch_read_cost_census.argtypes = [vp, i, vp, C.POINTER(i), C.POINTER(i)]
     L.ufm_batch_heuristic_multiplier.argtypes = [vp, C.POINTER(f)]
+    L.ufm_set_sensor.argtypes = [vp, vp, i, i, i, i]
+    L.ufm_set_survey.argtypes = [vp, vp, i, i]
+    L.ufm_set_survey_device.argtypes = [vp, vp, i, i]
+    L.ufm_reveal.argtypes = [vp, i, i, vp]
+    L.ufm_read_survey.argtypes = [vp, vp]
+    L.ufm_batch_set_sensor.argtypes = [vp, vp, i, i, i, i]
+    L.ufm_batch_set_survey.argtypes = [vp, i, vp, i, i]
+    L.ufm_batch_set_survey_device.argtypes = [vp, i, vp, i, i]
+    L.ufm_batch_reveal.argtypes = [vp, vp, vp]
+    L.ufm_batch_read_survey.argtypes = [vp, i, vp]
     _LIB = L
     return L
 
@@ -198,6 +210,29 @@ def _cspace_args(mask, anchor):
         raise UfmError("a footprint is a matrix")
     ar, ac = (-1, -1) if anchor is None else (int(anchor[0]), int(anchor[1]))
     return mask, mask.shape[1], mask.shape[0], ar, ac
+
+
+def sensor_disc(radius):
+    """The field of view harness.round_patch_update reveals (run_simulator.py:9-28), as ufm_set_sensor takes it: the (2 r + 1)^2 uint8 matrix
+    of x^2 + y^2 <= r^2 with the anchor at its centre."""
+    r = int(radius)
+    yy, xx = np.mgrid[-r:r + 1, -r:r + 1]
+    return (xx * xx + yy * yy <= r * r).astype(np.uint8)
+
+
+def _survey_args(raster, width=None, length=None):
+    """(pointer, width, length, on_device, the object to keep alive) of a survey: a host matrix, or a device buffer (anything with .ptr, e.g.
+    the tests' DeviceBytes) with its dimensions -- its own .shape = (length, width), or the two keywords"""
+    if hasattr(raster, "ptr"):
+        if width is None or length is None:
+            if not hasattr(raster, "shape"):
+                raise UfmError("a device survey needs width and length")
+            length, width = raster.shape
+        return raster.ptr, int(width), int(length), True, raster
+    raster = np.ascontiguousarray(raster, dtype=np.uint8)
+    if raster.ndim != 2:
+        raise UfmError("a survey is a matrix")
+    return raster.ctypes.data, raster.shape[1], raster.shape[0], False, raster
 
 
 def _read_census(call, what):
@@ -409,6 +444,30 @@ class Planner:
         _chk(self.L.ufm_heuristic_multiplier(self.h, C.byref(v)), "ufm_heuristic_multiplier")
         return v.value
 
+    def set_sensor(self, mask, anchor=None):
+        """ufm_set_sensor: the field of view (uint8 matrix, non-zero = seen; anchor (row, col), None: the centre); sensor_disc(r) is the
+        reference simulator's"""
+        mask, mw, mh, ar, ac = _cspace_args(mask, anchor)
+        _chk(self.L.ufm_set_sensor(self.h, mask.ctypes.data, mw, mh, ar, ac), "ufm_set_sensor")
+
+    def set_survey(self, raster, width=None, length=None):
+        """ufm_set_survey / _device: what the sensor would see, [length][width] like the map -- a host matrix, or a device buffer (.ptr)
+        with width and length"""
+        ptr, width, length, dev, keep = _survey_args(raster, width, length)
+        fn = self.L.ufm_set_survey_device if dev else self.L.ufm_set_survey
+        _chk(fn(self.h, ptr, width, length), "ufm_set_survey")
+
+    def reveal(self, row, col, count=False):
+        """ufm_reveal: uncover the field of view around cell (row, col).  count: wait and return the number of cells that changed"""
+        n = C.c_uint64(0)
+        _chk(self.L.ufm_reveal(self.h, int(row), int(col), C.addressof(n) if count else None), "ufm_reveal")
+        return int(n.value) if count else None
+
+    def read_survey(self, width, length):
+        m = np.empty((length, width), dtype=np.uint8)
+        _chk(self.L.ufm_read_survey(self.h, m.ctypes.data), "ufm_read_survey")
+        return m
+
     def check_layout(self):
         """(ring entries, cost-window bytes) that differ from the values they copy; (0, 0) when sound"""
         bad = (C.c_uint64 * 2)()
@@ -542,6 +601,32 @@ class BatchPlanner:
         v = C.c_float(0.0)
         _chk(self.L.ufm_batch_heuristic_multiplier(self.h, C.byref(v)), "ufm_batch_heuristic_multiplier")
         return v.value
+
+    def set_sensor(self, mask, anchor=None):
+        """as Planner.set_sensor, for every map on every shard"""
+        mask, mw, mh, ar, ac = _cspace_args(mask, anchor)
+        _chk(self.L.ufm_batch_set_sensor(self.h, mask.ctypes.data, mw, mh, ar, ac), "ufm_batch_set_sensor")
+
+    def set_survey(self, i, raster, width=None, length=None):
+        """as Planner.set_survey, for map i"""
+        ptr, width, length, dev, keep = _survey_args(raster, width, length)
+        fn = self.L.ufm_batch_set_survey_device if dev else self.L.ufm_batch_set_survey
+        _chk(fn(self.h, int(i), ptr, width, length), "ufm_batch_set_survey")
+
+    def reveal(self, centres, count=False):
+        """ufm_batch_reveal: one launch per device for all maps; centres [n][2] = (row, col), row < 0 skips the map.  count: wait and
+        return the changed cells per map (uint64 [n])"""
+        c = np.ascontiguousarray(centres, np.int32).reshape(-1, 2)
+        if len(c) != self.n:
+            raise UfmError("one centre per map")
+        out = np.zeros(self.n, np.uint64)
+        _chk(self.L.ufm_batch_reveal(self.h, c.ctypes.data, out.ctypes.data if count else None), "ufm_batch_reveal")
+        return out if count else None
+
+    def read_survey(self, i, width, length):
+        m = np.empty((length, width), dtype=np.uint8)
+        _chk(self.L.ufm_batch_read_survey(self.h, int(i), m.ctypes.data), "ufm_batch_read_survey")
+        return m
 
     def set_start(self, i, x, y):
         _chk(self.L.ufm_batch_set_start(self.h, i, float(x), float(y)), "ufm_batch_set_start")

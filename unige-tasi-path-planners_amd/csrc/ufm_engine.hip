@@ -49,6 +49,7 @@ namespace {
 #include "ufm_region.h"
 #include "ufm_cspace.h"
 #include "ufm_census.h"
+#include "ufm_sensor.h"
 
 #include "ufm_host.h"
 #include "ufm_delta.h"
@@ -315,6 +316,18 @@ static int census_sum(Engine *const *shards, int per, int first, int count, uint
 int ufm_track_costs(ufm_t *p, int enable) { return p ? engine_track_costs(p->e, enable) : UFM_ERR_INVALID; }
 int ufm_read_cost_census(ufm_t *p, uint64_t hist[256], int *min_cost, int *max_cost) { return p ? census_sum(&p->e, 1, 0, 1, hist, min_cost, max_cost) : UFM_ERR_INVALID; }
 int ufm_heuristic_multiplier(ufm_t *p, float *used) { if (!p || !used) return UFM_ERR_INVALID; *used = p->e->last_multiplier; return UFM_OK; }
+int ufm_set_sensor(ufm_t *p, const uint8_t *mask, int mw, int mh, int anchor_row, int anchor_col) { return p ? engine_set_sensor(p->e, mask, mw, mh, anchor_row, anchor_col) : UFM_ERR_INVALID; }
+int ufm_set_survey(ufm_t *p, const uint8_t *host_survey, int width, int length) { return p ? engine_set_survey(p->e, 0, host_survey, false, width, length) : UFM_ERR_INVALID; }
+int ufm_set_survey_device(ufm_t *p, const uint8_t *dev_survey, int width, int length) { return p ? engine_set_survey(p->e, 0, dev_survey, true, width, length) : UFM_ERR_INVALID; }
+int ufm_read_survey(ufm_t *p, uint8_t *host_survey) { return p ? engine_read_survey(p->e, 0, host_survey) : UFM_ERR_INVALID; }
+int ufm_reveal(ufm_t *p, int row, int col, uint64_t *changed) {
+    if (!p) return UFM_ERR_INVALID;
+    const int32_t c[2] = {row, col};
+    if (row < 0) return UFM_ERR_INVALID;        // (a single planner has no map to skip)
+    HIPCHK(hipSetDevice(p->e->device));
+    { int rc = p->e->reveal(c); if (rc != UFM_OK) return rc; }
+    return changed ? p->e->reveal_counts(c, changed) : UFM_OK;
+}
 int ufm_set_profiling(ufm_t *p, int enable) { if (!p) return UFM_ERR_INVALID; p->e->profiling = enable != 0; return UFM_OK; }
 void *ufm_stream(ufm_t *p) { return p ? (void *)p->e->stream : nullptr; }
 
@@ -457,6 +470,35 @@ int ufm_batch_set_cspace(ufm_batch_t *b, const uint8_t *mask, int mw, int mh, in
     if (!b || b->shards.empty()) return UFM_ERR_INVALID;
     for (Engine *e : b->shards) for (const MapState &ms : e->maps) if (ms.have_map) return UFM_ERR_INVALID;   // (all shards or none)
     for (Engine *e : b->shards) { const int rc = engine_set_cspace(e, mask, mw, mh, anchor_row, anchor_col); if (rc != UFM_OK) return rc; }
+    return UFM_OK;
+}
+int ufm_batch_set_sensor(ufm_batch_t *b, const uint8_t *mask, int mw, int mh, int anchor_row, int anchor_col) {
+    if (!b || b->shards.empty() || !sensor_valid(mask, mw, mh, anchor_row, anchor_col)) return UFM_ERR_INVALID;   // (all shards or none)
+    for (Engine *e : b->shards) { const int rc = engine_set_sensor(e, mask, mw, mh, anchor_row, anchor_col); if (rc != UFM_OK) return rc; }
+    return UFM_OK;
+}
+int ufm_batch_set_survey(ufm_batch_t *b, int i, const uint8_t *host_survey, int width, int length) { UFM_BATCH_MAP(b, i); return engine_set_survey(e, li, host_survey, false, width, length); }
+int ufm_batch_set_survey_device(ufm_batch_t *b, int i, const uint8_t *dev_survey, int width, int length) { UFM_BATCH_MAP(b, i); return engine_set_survey(e, li, dev_survey, true, width, length); }
+int ufm_batch_read_survey(ufm_batch_t *b, int i, uint8_t *host_survey) { UFM_BATCH_MAP(b, i); return engine_read_survey(e, li, host_survey); }
+// The maps grouped by the device that owns them (contiguous blocks: a shard's centres are a slice of the caller's array): every shard is
+// checked before any of them launches; then one k_reveal per shard, queued side by side, and only then the counts are waited for.
+int ufm_batch_reveal(ufm_batch_t *b, const int32_t *centres, uint64_t *changed) {
+    if (!b || b->shards.empty() || !centres) return UFM_ERR_INVALID;
+    for (size_t s = 0; s < b->shards.size(); ++s) {
+        const int rc = b->shards[s]->reveal_check(centres + 2 * s * (size_t)b->per);
+        if (rc != UFM_OK) return rc;
+    }
+    for (size_t s = 0; s < b->shards.size(); ++s) {
+        HIPCHK(hipSetDevice(b->shards[s]->device));
+        const int rc = b->shards[s]->reveal(centres + 2 * s * (size_t)b->per);
+        if (rc != UFM_OK) return rc;
+    }
+    if (!changed) return UFM_OK;
+    for (size_t s = 0; s < b->shards.size(); ++s) {
+        HIPCHK(hipSetDevice(b->shards[s]->device));
+        const int rc = b->shards[s]->reveal_counts(centres + 2 * s * (size_t)b->per, changed + s * (size_t)b->per);
+        if (rc != UFM_OK) return rc;
+    }
     return UFM_OK;
 }
 int ufm_batch_set_profiling(ufm_batch_t *b, int enable) {

@@ -279,6 +279,23 @@ struct Engine {
     void census_publish() { k_census_publish<<<1, CENSUS_BINS, 0, stream>>>(d_census, nmaps, h_cen, h_cen_flag, ++cen_seq); }
     int census_minmax(int *mn, int *mx);
     void census_free();
+    // Sensor reveal (ufm_set_sensor / ufm_set_survey / ufm_reveal; ufm_sensor.h).  No sensor and no survey -- the default --
+    // nothing below exists or runs.  d_survey holds what the sensor would see, per map; a reveal makes the dense patch Q of every map's field
+    // of view in ONE launch (k_reveal) into that map's slot of d_reveal and hands the slot to patch_raw() / patch() as the caller's device
+    // patch would be handed -- so whatever a patch does (raw store, re-dilation, census, seeding, the block kernel, deferral) a reveal does.
+    // A deferred patch may point into d_reveal: reveal() applies what is held before k_reveal writes the slots again.
+    SensorShape sensor;
+    uint8_t *d_sensor = nullptr;     // the mask's bytes, room for SENSOR_MAX^2
+    uint8_t *d_survey = nullptr;     // [nmaps][L][W]; dropped with the rasters (release())
+    std::vector<uint8_t> have_survey;    // [nmaps]
+    uint8_t *d_reveal = nullptr;     // [nmaps] slots of sensor_slot_stride() bytes
+    size_t d_reveal_cap = 0;
+    unsigned int *d_reveal_cnt = nullptr;    // [nmaps]: changed cells of the last reveal
+    int32_t *h_centres = nullptr;    // [nmaps][2], pinned + mapped: k_reveal reads the centres from here
+    bool reveal_busy = false;        // a k_reveal that is only queued may still read h_centres
+    int reveal_check(const int32_t *centres) const;
+    int reveal(const int32_t *centres);
+    int reveal_counts(const int32_t *centres, uint64_t *changed);
     // step deltas (ufm_track_changes / ufm_read_changes, ufm_delta.h): nothing below exists unless a caller turned tracking on
     bool track = false;
     float *trk_g = nullptr;          // the baseline: the field as the caller was last told, in the layout of P.G (same gstride)
@@ -306,6 +323,9 @@ void Engine::release() {
     for (void *q : ptrs) if (q) hipFree(q);
     if (d_raw) hipFree(d_raw);
     d_raw = nullptr;
+    if (d_survey) hipFree(d_survey);     // (a survey belongs to rasters of these dimensions)
+    d_survey = nullptr;
+    std::fill(have_survey.begin(), have_survey.end(), (uint8_t)0);
     P = DevParams{};                     // every pointer null again: a failed alloc() can be released, and released twice
     d_scratch = nullptr;
     allocated = false;
@@ -810,6 +830,68 @@ void Engine::census_free() {
     census_on = auto_multiplier = false;
 }
 
+// ---- the sensor reveal: a move uncovers the survey raster's field of view, as a patch made on the device ----
+// everything a reveal of these centres ([nmaps][2], row < 0: skipped) needs; nothing is launched or written
+int Engine::reveal_check(const int32_t *centres) const {
+    if (!centres || !sensor.set || !allocated || !d_survey) return UFM_ERR_INVALID;
+    for (int m = 0; m < nmaps; ++m) {
+        if (centres[2 * m] < 0) continue;
+        if (!maps[m].have_map || !have_survey[m] || !sensor_centre_ok(centres[2 * m], centres[2 * m + 1], L, W)) return UFM_ERR_INVALID;
+    }
+    return UFM_OK;
+}
+// One k_reveal for all maps, then every map's slot through the route its device patch would take.  As in patch_raw(), whatever can fail
+// -- applying what is held, the growth of the buffers -- comes before the first write to a raster.
+int Engine::reveal(const int32_t *centres) {
+    { int rc = reveal_check(centres); if (rc != UFM_OK) return rc; }
+    bool any = false;
+    for (int m = 0; m < nmaps; ++m) any = any || centres[2 * m] >= 0;
+    if (!any) return UFM_OK;
+    // held patches first, in order -- and a deferred one may point into the slots k_reveal is about to overwrite
+    { int rc = flush_deferred(); if (rc != UFM_OK) return rc; }
+    const size_t stride = sensor_slot_stride(sensor.mw, sensor.mh), need = stride * (size_t)nmaps;
+    if (need > d_reveal_cap) { int rc = regrow(stream, need, d_reveal_cap, need, d_reveal); if (rc != UFM_OK) return rc; }
+    size_t largest = (size_t)sensor.mw * sensor.mh;                       // the largest patch any map's slot can become
+    if (cs.on) {
+        largest = (size_t)(sensor.mw + cs.mw - 1) * (size_t)(sensor.mh + cs.mh - 1);
+        if (largest > d_cs_patch_cap) {
+            const size_t cap = std::max<size_t>(largest, 4096);
+            { int rc = regrow(stream, cap, d_cs_patch_cap, cap, d_cs_patch); if (rc != UFM_OK) return rc; }
+        }
+    }
+    { int rc = ensure_pmask(largest); if (rc != UFM_OK) return rc; }
+    if (reveal_busy) { HIPCHK(hipStreamSynchronize(stream)); reveal_busy = false; }
+    std::memcpy(h_centres, centres, sizeof(int32_t) * 2 * (size_t)nmaps);
+    __atomic_thread_fence(__ATOMIC_RELEASE);
+    HIPCHK(hipMemsetAsync(d_reveal_cnt, 0, sizeof(unsigned int) * nmaps, stream));
+    RevealJob j{};
+    j.mask = d_sensor; j.survey = d_survey; j.cur = cs.on ? d_raw : P.cost; j.slots = d_reveal; j.count = d_reveal_cnt; j.centres = h_centres;
+    j.cstride = P.cstride; j.slot_stride = stride;
+    j.L = L; j.W = W; j.mh = sensor.mh; j.mw = sensor.mw; j.ar = sensor.ar; j.ac = sensor.ac;
+    k_reveal<<<dim3(sensor_grid_x(sensor.mw, sensor.mh), nmaps), SENSOR_THREADS, 0, stream>>>(j);
+    HIPCHK(hipGetLastError());
+    reveal_busy = true;
+    for (int m = 0; m < nmaps; ++m) {
+        if (centres[2 * m] < 0) continue;
+        const SensorRect r = sensor_place(centres[2 * m], centres[2 * m + 1], sensor.mh, sensor.mw, sensor.ar, sensor.ac, L, W);
+        const uint8_t *slot = d_reveal + stride * (size_t)m;
+        const int rc = cs.on ? patch_raw(m, slot, r.x, r.y, r.w, r.h) : patch(m, slot, r.x, r.y, r.w, r.h, true);
+        if (rc != UFM_OK) return rc;
+    }
+    return UFM_OK;
+}
+// the counts of the last reveal, once the stream has run: changed[m], 0 for a map that was skipped
+int Engine::reveal_counts(const int32_t *centres, uint64_t *changed) {
+    std::vector<unsigned int> cnt((size_t)nmaps, 0u);
+    bool any = false;
+    for (int m = 0; m < nmaps; ++m) any = any || centres[2 * m] >= 0;
+    if (any) HIPCHK(hipMemcpyAsync(cnt.data(), d_reveal_cnt, sizeof(unsigned int) * nmaps, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    reveal_busy = false;
+    for (int m = 0; m < nmaps; ++m) changed[m] = centres[2 * m] >= 0 ? cnt[m] : 0u;
+    return UFM_OK;
+}
+
 // ---- a step: ReplannerBase::step (ReplannerBase.h:43-75) --------------------------------------------------------------------
 // plan_step (ufm_route.h) says what the step is and which route a replan takes; the parts below act on that, in the order they are written.
 
@@ -1255,6 +1337,7 @@ int Engine::step(ufm_stats *out, const float *auto_mult) {
     st.queued_raise = (uint32_t)(h_ctr->cnt[Q_RAISE][iter[Q_RAISE] % 3] + h_ctr->npark[Q_RAISE]);
     st.graphs_instantiated = graphs_made;
     st.region_replans = region_runs; st.region_replans_done = region_done;
+    reveal_busy = false;        // (the step has waited for kernels queued behind any reveal)
     st.u_ms = (float)r.u_acc;   // seeding + invalidation (the reference's update())
     st.p_ms = (float)r.p_acc;   // propagation + finalisation (the reference's plan())
     last = st;
@@ -1336,6 +1419,8 @@ int engine_destroy(Engine *e) {
     for (hipEvent_t v : e->reg_ev) if (v) hipEventDestroy(v);
     for (hipEvent_t v : e->trk_ev) if (v) hipEventDestroy(v);
     e->census_free();
+    free_all(hipFree, e->d_sensor, e->d_reveal, e->d_reveal_cnt);
+    free_all(hipHostFree, e->h_centres);
     free_all(hipFree, e->d_cs_patch, e->d_patch, e->d_pmask, e->d_field, e->d_info, e->d_jobs, e->d_path);
     free_all(hipHostFree, e->h_jobs, e->h_path, e->h_patch, e->h_lazy);
     e->drop_graphs();
@@ -1415,6 +1500,55 @@ int engine_read_raw_map(Engine *e, int m, uint8_t *host_map) {
     if (!e || !host_map || !e->cs.on || !e->allocated || m < 0 || m >= e->nmaps || !e->maps[m].have_map) return UFM_ERR_INVALID;
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipMemcpyAsync(host_map, e->d_raw + (size_t)m * e->P.cstride, e->P.cstride, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return UFM_OK;
+}
+
+// ufm_set_sensor / ufm_batch_set_sensor: the field of view, set or replaced between any two calls; needs no map
+int engine_set_sensor(Engine *e, const uint8_t *mask, int mw, int mh, int ar, int ac) {
+    if (!e) return UFM_ERR_INVALID;
+    SensorShape s;
+    if (!sensor_pack(mask, mw, mh, ar, ac, &s)) return UFM_ERR_INVALID;
+    HIPCHK(hipSetDevice(e->device));
+    if (!e->d_sensor) {
+        const int rc = [&]() -> int {
+            HIPCHK(hipMalloc(&e->d_sensor, (size_t)SENSOR_MAX * SENSOR_MAX));
+            HIPCHK(hipMalloc(&e->d_reveal_cnt, sizeof(unsigned int) * e->nmaps));
+            HIPCHK(hipHostMalloc(&e->h_centres, sizeof(int32_t) * 2 * e->nmaps, hipHostMallocMapped));
+            return UFM_OK;
+        }();
+        if (rc != UFM_OK) {
+            free_all(hipFree, e->d_sensor, e->d_reveal_cnt); free_all(hipHostFree, e->h_centres);
+            e->d_sensor = nullptr; e->d_reveal_cnt = nullptr; e->h_centres = nullptr;
+            return rc;
+        }
+        e->have_survey.resize((size_t)e->nmaps, 0);
+    }
+    // (a reveal that is only queued reads the old mask: wait for it, then replace the bytes)
+    HIPCHK(hipStreamSynchronize(e->stream));
+    e->reveal_busy = false;
+    HIPCHK(hipMemcpy(e->d_sensor, mask, (size_t)mw * mh, hipMemcpyHostToDevice));
+    e->sensor = s;
+    return UFM_OK;
+}
+// ufm_set_survey* / ufm_batch_set_survey*: what the sensor would see of map m, for the raster that map has
+int engine_set_survey(Engine *e, int m, const uint8_t *src, bool on_device, int width, int length) {
+    if (!e || !src || m < 0 || m >= e->nmaps || !e->allocated || !e->maps[m].have_map || width != e->W || length != e->L) return UFM_ERR_INVALID;
+    HIPCHK(hipSetDevice(e->device));
+    if (!e->d_survey) {
+        if (hipMalloc(&e->d_survey, e->P.cstride * e->nmaps) != hipSuccess) { (void)hipGetLastError(); e->d_survey = nullptr; return UFM_ERR_NOMEM; }
+        e->have_survey.assign((size_t)e->nmaps, 0);
+    }
+    HIPCHK(hipMemcpyAsync(e->d_survey + (size_t)m * e->P.cstride, src, e->P.cstride, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));      // (the caller's buffer is free again when the call returns)
+    e->reveal_busy = false;
+    e->have_survey[m] = 1;
+    return UFM_OK;
+}
+int engine_read_survey(Engine *e, int m, uint8_t *host_survey) {
+    if (!e || !host_survey || m < 0 || m >= e->nmaps || !e->allocated || !e->d_survey || !e->have_survey[m]) return UFM_ERR_INVALID;
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipMemcpyAsync(host_survey, e->d_survey + (size_t)m * e->P.cstride, e->P.cstride, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     return UFM_OK;
 }

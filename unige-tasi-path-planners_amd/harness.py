@@ -166,7 +166,7 @@ class Pipes:
 
 def run_mission(cmd, pipe_to_planner, pipe_from_planner, img_h, start, goal, radius=5, cspace_diameter=1,
                 low_res_penalty=10, use_heuristic=False, max_moves=10000, on_map=None, on_move=None, display_shift=0.0,
-                append_pipes=True, tof=False, on_expanded=None, planner_inflates=False, planner_min_cost=False):
+                append_pipes=True, tof=False, on_expanded=None, planner_inflates=False, planner_min_cost=False, planner_senses=False):
     """One mission as Tests/run_test.py:85-177 runs it: launch the planner process `cmd`, send the
     C-space of the low-resolution map, then per robot position reveal the disc of radius `radius`,
     send its bounding patch and the heuristic hint, receive the planned path.  start / goal are
@@ -179,7 +179,10 @@ def run_mission(cmd, pipe_to_planner, pipe_from_planner, img_h, start, goal, rad
     planner_inflates: the planner process dilates on its own (ufm_planner --inflate D with D = cspace_diameter): the low-resolution map and
     the patches are sent RAW, and on_map / on_move get what was sent; min_cost is still taken from the inflated map.
     planner_min_cost: the planner process finds the heuristic multiplier itself (ufm_planner --auto-heuristic): the hint on the wire is a
-    placeholder, int(data_l.min()) -- and together with planner_inflates nothing is dilated here at all.  Returns the list of positions visited and whether the planner reported the end."""
+    placeholder, int(data_l.min()) -- and together with planner_inflates nothing is dilated here at all.
+    planner_senses: the planner process uncovers the field of view itself (ufm_planner --sense R with R = radius): the high-resolution data
+    goes out ONCE, directly after the map, and every move's patch message is empty (h = w = 0, no bytes); the harness still keeps its own
+    low-resolution map up to date, so on_move reports the patch the reference would have sent.  Returns the list of positions visited and whether the planner reported the end."""
     for p in (pipe_to_planner, pipe_from_planner):
         if not os.path.exists(p):
             os.mkfifo(p)
@@ -199,6 +202,8 @@ def run_mission(cmd, pipe_to_planner, pipe_from_planner, img_h, start, goal, rad
         height, width = cspace.shape
         io.send("ii", width, height)
         io.send_bytes(np.ascontiguousarray(data_l if planner_inflates else cspace).tobytes())
+        if planner_senses:
+            io.send_bytes(np.ascontiguousarray(data_h).tobytes())
         if start is not None:
             io.send("ffffB", float(start[0]), float(start[1]), float(goal[0]), float(goal[1]), 1 if tof else 0)
         io.send("i", min_cost)
@@ -225,8 +230,11 @@ def run_mission(cmd, pipe_to_planner, pipe_from_planner, img_h, start, goal, rad
             if use_heuristic:
                 min_cost = int(data_l.min()) if planner_min_cost else int(cspace.min())
             io.send("b", 1)
-            io.send("iiii", top, left, patch.shape[0], patch.shape[1])
-            io.send_bytes(patch.tobytes())
+            if planner_senses:
+                io.send("iiii", top, left, 0, 0)
+            else:
+                io.send("iiii", top, left, patch.shape[0], patch.shape[1])
+                io.send_bytes(patch.tobytes())
             io.send("i", min_cost)
             io.flush()
             assert io.recv("b") == (3,)

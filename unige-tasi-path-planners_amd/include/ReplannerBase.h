@@ -70,6 +70,20 @@ class ReplannerBase {
   void set_cspace(const uint8_t *mask, int mw, int mh, int anchor_row = -1, int anchor_col = -1) {
     check(ufm_set_cspace(handle_, mask, mw, mh, anchor_row, anchor_col));
   }
+  /** Sensor reveal on the device (ufm_set_sensor / ufm_set_survey / ufm_reveal; no reference counterpart: the reference's simulator keeps
+   *  the high-resolution raster and ships the revealed rectangle every move, run_simulator.py:9-28,177): the field of view mask[mh][mw]
+   *  with its anchor (-1, -1: the centre), the survey raster -- what the sensor would see, of the map's size, after set_map --, and
+   *  reveal(row, col), which uncovers the field of view around that cell as a patch_map of those bytes would; changed (optional) gets the
+   *  number of cells that changed and makes the call wait.  `grid` keeps the raster the host handed over: it does not follow reveals. */
+  void set_sensor(const uint8_t *mask, int mw, int mh, int anchor_row = -1, int anchor_col = -1) {
+    check(ufm_set_sensor(handle_, mask, mw, mh, anchor_row, anchor_col));
+  }
+  void set_survey(const std::shared_ptr<uint8_t> &survey, int w, int h) { check(ufm_set_survey(handle_, survey.get(), w, h)); }
+  int reveal(int row, int col, uint64_t *changed = nullptr) {
+    const int rc = ufm_reveal(handle_, row, col, changed);
+    if (rc != UFM_OK) last_error = rc;
+    return rc;
+  }
   /** Cost census (ufm_track_costs; no reference counterpart: the reference's simulator takes cv2.minMaxLoc of the map it inflated itself,
    *  run_simulator.py:152,183): exact counts of the PLANNING raster's values, kept under patches.  min_cost(): the smallest value present,
    *  -1 if the census is off or no map is set; cost_census(): all 256 counters, returns the ufm code. */
