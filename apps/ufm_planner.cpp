@@ -12,7 +12,7 @@
 // LinearInterpolationPathExtractor, reset / set_* / patch_map / step / extract_path, u_time,
 // p_time, e_time, map.size(), map.buckets.
 //
-//   ufm_planner [--planner FD|SG|DFM] [--level K] [--max-moves N] [--verify-follow] [--inflate D] [--auto-heuristic] [--sense R] <fifo_in> <fifo_out>
+//   ufm_planner [--planner FD|SG|DFM] [--level K] [--max-moves N] [--verify-follow] [--inflate D] [--auto-heuristic] [--sense R] [--image K P] <fifo_in> <fifo_out>
 //        start, goal and the `tof` flag arrive in-band after the map (DFM/main.cpp:62-67)
 //   ufm_planner [...] <mapfile> <from_x> <from_y> <to_x> <to_y> <cspace> <fifo_in> <fifo_out> <gui> <tof> <outpath>
 //        the 11-argument form of FDSTAR/main.cpp:16-31 and SGDFM/main.cpp
@@ -27,6 +27,11 @@
 // and no bytes, and before each step the planner uncovers the disc x^2 + y^2 <= R^2 around the cell it has just reported: each
 // coordinate AS SENT (the cell planners' display shift included) rounded half-to-even, as Python's round does at Tests/run_test.py:143.
 // Composes with --inflate and --auto-heuristic: the simulator then touches no raster after the start.
+// --image K P: the planner prepares the map itself (ufm_set_image).  Where the map raster would arrive the wire carries the grey-scale
+// BITMAP, framed the same way (width, height, bytes, then min_cost as always); the planner blurs it with ufm_gaussian_taps(K), K odd,
+// 1 .. 31, complements it and adds the saturating penalty P, 0 .. 255 -- the simulator's simulation_data (run_simulator.py:106-113,148) --
+// and the same launch leaves the complemented bitmap as the survey: with --sense R no separate survey message is sent.  Composes with
+// --inflate and --auto-heuristic: the simulator then hands over a bitmap and positions, nothing else.
 // With `tof` the expanded-element dump after every step is kept up to date from the steps' deltas (ExpandedMap::follow_changes), not
 // read back whole; --verify-follow also builds it the old way every step -- a read of the whole field through a second view of the
 // same planner -- and ends the run (exit code 3) if the two differ in any element, value, Info or order.
@@ -87,6 +92,8 @@ struct Options {
   int inflate = 0;           // --inflate D: footprint diameter (<= 1: off)
   bool auto_heuristic = false;   // --auto-heuristic: the multiplier follows the engine's planning raster
   int sense = -1;            // --sense R: radius of the field of view the planner uncovers itself (< 0: off)
+  int image = 0;             // --image K P: the wire carries the bitmap, blurred here with K Gaussian taps (0: off) ...
+  int image_penalty = 0;     // ... and P added, saturating
   std::string fifo_in, fifo_out;
 };
 
@@ -106,7 +113,7 @@ int serve(Options opt, bool cell_planner, bool indirect) {
   auto data = byte_block((size_t)width * height);
   io.get_bytes(data.get(), (size_t)width * height);
   std::shared_ptr<uint8_t> survey;
-  if (opt.sense >= 0) {
+  if (opt.sense >= 0 && !opt.image) {
     survey = byte_block((size_t)width * height);
     io.get_bytes(survey.get(), (size_t)width * height);
   }
@@ -136,7 +143,14 @@ int serve(Options opt, bool cell_planner, bool indirect) {
         disc[(size_t)a * n + b] = (double)((b - r) * (b - r)) / (double)(r * r) + (double)((a - r) * (a - r)) / (double)(r * r) <= 1.0;
     planner.set_cspace(disc.data(), n, n);
   }
-  planner.set_map(data, width, height);
+  if (opt.image) {
+    uint16_t taps[31];
+    if (ufm_gaussian_taps(opt.image, taps) != UFM_OK) throw std::runtime_error("--image: K is odd, 1 .. 31");
+    planner.set_image(data, width, height, taps, opt.image, opt.image_penalty);
+    if (planner.last_error != UFM_OK) throw std::runtime_error("set_image failed with " + std::to_string(planner.last_error));
+  } else {
+    planner.set_map(data, width, height);
+  }
   // --sense: the disc of harness.round_patch_update / run_simulator.py:9-28.  A position on the map's far border rounds to a cell one
   // beyond the last (nodes run 0 .. length): the simulator's disc then hangs over the border, here the anchor moves by that one cell.
   std::vector<uint8_t> fov;
@@ -157,7 +171,7 @@ int serve(Options opt, bool cell_planner, bool indirect) {
     fov.resize((size_t)fov_n * fov_n);
     for (int a = 0; a < fov_n; ++a)
       for (int b = 0; b < fov_n; ++b) fov[(size_t)a * fov_n + b] = (a - r) * (a - r) + (b - r) * (b - r) <= r * r;
-    planner.set_survey(survey, width, height);
+    if (!opt.image) planner.set_survey(survey, width, height);        // (--image: set_image has left the survey)
     if (planner.last_error != UFM_OK) throw std::runtime_error("set_survey failed with " + std::to_string(planner.last_error));
   }
   // the dump after every step: follow the steps' deltas on the host instead of reading the whole field back each time
@@ -239,7 +253,7 @@ int serve(Options opt, bool cell_planner, bool indirect) {
 
 void usage(const char *argv0) {
   std::fprintf(stderr,
-               "Usage:\n\t%s [--planner FD|SG|DFM] [--level K] [--max-moves N] [--verify-follow] [--inflate D] [--auto-heuristic] [--sense R] <fifo_in> <fifo_out>\n"
+               "Usage:\n\t%s [--planner FD|SG|DFM] [--level K] [--max-moves N] [--verify-follow] [--inflate D] [--auto-heuristic] [--sense R] [--image K P] <fifo_in> <fifo_out>\n"
                "\t%s [...] <mapfile> <from_x> <from_y> <to_x> <to_y> <cspace> <fifo_in> <fifo_out> <gui> <tof> <outpath>\n",
                argv0, argv0);
 }
@@ -272,6 +286,7 @@ int main(int argc, char **argv) {
     else if (a == "--inflate" && i + 1 < argc) opt.inflate = std::atoi(argv[++i]);
     else if (a == "--auto-heuristic") opt.auto_heuristic = true;
     else if (a == "--sense" && i + 1 < argc) opt.sense = std::atoi(argv[++i]);
+    else if (a == "--image" && i + 2 < argc) { opt.image = std::atoi(argv[++i]); opt.image_penalty = std::atoi(argv[++i]); }
     else if (a == "-h" || a == "--help") { usage(argv[0]); return 0; }
     else pos.push_back(a);
   }

@@ -337,6 +337,37 @@ int ufm_set_survey_device(ufm_t *p, const uint8_t *dev_survey, int width, int le
 int ufm_reveal(ufm_t *p, int row, int col, uint64_t *changed);
 int ufm_read_survey(ufm_t *p, uint8_t *host_survey);
 
+/* ---- map preparation: a grey-scale bitmap becomes the map and the survey, on the device.  The one raster operation of the reference's
+ * simulator that reads and writes the whole raster is simulation_data (Simulator/simulator/run_simulator.py:106-113,148,
+ * Tests/run_test.py:101): from the bitmap the high-resolution costs ~pixel, 0 -> 1 -- what ufm_set_survey is handed -- and the
+ * low-resolution costs ~GaussianBlur(pixel), 0 -> 1, plus a saturating penalty -- what ufm_set_map is handed.  Here one call takes the
+ * bitmap, a third of the bytes, and one launch makes both rasters where the engine keeps them.  OPT-IN: a caller that never calls it sees
+ * no allocation, no launch and no other route.
+ * The filter is DATA, not a size, as the footprint of ufm_set_cspace and the field of view of ufm_set_sensor are: taps[ntaps], the 8-bit
+ * fixed-point coefficients of one axis, the same for rows and columns; ntaps odd, 1 .. 31, every tap <= 256, their sum exactly 256;
+ * ntaps == 1 ({256}) is "no blur".
+ * ufm_gaussian_taps(ksize, taps): host arithmetic only, no device.  Writes the ksize taps cv2.GaussianBlur(img, (k, k), 0) applies to 8-bit
+ * images: the fixed table for k <= 7, else the Gaussian of sigma = 0.3 ((k - 1) / 2 - 1) + 0.8; every coefficient x 256 and rounded, the
+ * rounding error carried to the next tap, the centre taking what is left of 256 (k = 13: 1 5 10 19 30 41 44 41 30 19 10 5 1).  ksize odd,
+ * 1 .. 31; UFM_ERR_INVALID otherwise or for NULL taps.  Only k = 3 and k = 13 are pinned to OpenCV, by the reference's recorded mission
+ * logs (tests/test_reference_mission.py); the other sizes follow the same published rule and are not a claim about cv2.
+ * ufm_set_image / ufm_set_image_device, defined by equivalence.  image[length][width], row-major uint8.  H[i][j] = ~image[i][j], 0
+ * replaced by 1.  L: the image padded by reflect-101 (numpy.pad(mode="reflect")), the horizontal pass, then the vertical pass, both in
+ * exact integers, ONE rounding (v + 32768) >> 16, the complement, 0 replaced by 1, min(. + penalty, 255).  The call leaves the handle in
+ * exactly the state ufm_set_map(p, L, width, length) followed by ufm_set_survey(p, H, width, length) would: the raw store and
+ * planning == dilate(raw) with a footprint, the census built and published, the cost windows and the mean traversable cost, the
+ * step-delta baseline empty, the goal's validity, the survey of that map set.  A sensor need not be set.  An earlier survey of that map
+ * is REPLACED -- unlike a plain ufm_set_map of the same dimensions, which keeps it.
+ * The image is read at the call, and the call returns with the caller's buffer free again; the device form is stream-ordered on the
+ * engine's stream (ufm_stream), like ufm_set_map_device.
+ * UFM_ERR_INVALID, before anything is launched, allocated or written, the handle staying usable: a NULL handle, image or taps; width or
+ * length <= 0; ntaps even or outside 1 .. 31; a tap > 256 or a sum other than 256; ntaps / 2 >= min(width, length) -- a single reflection
+ * must suffice, the only border case defined --; penalty outside 0 .. 255; a batch index outside the batch; a batch map whose size
+ * differs from the other maps'. ---- */
+int ufm_gaussian_taps(int ksize, uint16_t *taps);
+int ufm_set_image(ufm_t *p, const uint8_t *host_image, int width, int length, const uint16_t *taps, int ntaps, int penalty);
+int ufm_set_image_device(ufm_t *p, const uint8_t *dev_image, int width, int length, const uint16_t *taps, int ntaps, int penalty);
+
 /* ---- measurement hooks ---- */
 int ufm_set_profiling(ufm_t *p, int enable);   /* HIP-event timing of every relax launch */
 void *ufm_stream(ufm_t *p);                    /* hipStream_t the kernels run on */
@@ -407,6 +438,10 @@ int ufm_batch_set_survey_device(ufm_batch_t *b, int i, const uint8_t *dev_survey
 int ufm_batch_reveal(ufm_batch_t *b, const int32_t *centres /* [n_maps][2] = (row, col); row < 0: this map is skipped */,
                      uint64_t *changed /* [n_maps] or NULL */);
 int ufm_batch_read_survey(ufm_batch_t *b, int i, uint8_t *host_survey);
+/* as ufm_set_image / ufm_set_image_device, for map i: one launch per call, into that map's slots on the shard that owns it */
+int ufm_batch_set_image(ufm_batch_t *b, int i, const uint8_t *host_image, int width, int length, const uint16_t *taps, int ntaps, int penalty);
+int ufm_batch_set_image_device(ufm_batch_t *b, int i, const uint8_t *dev_image, int width, int length, const uint16_t *taps, int ntaps,
+                               int penalty);
 /* all maps in one launch: path_xy [n_maps][cap_points][2], step_costs [n_maps][cap_costs], info [n_maps] */
 int ufm_batch_extract_path(ufm_batch_t *b, int max_steps, int lookahead, int allow_indirect,
                            float *path_xy, int cap_points, float *step_costs, int cap_costs, ufm_path_info *info);

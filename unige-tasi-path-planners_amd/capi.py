@@ -31,6 +31,7 @@ SYMBOLS = [
     "ufm_batch_track_costs", "ufm_batch_read_cost_census", "ufm_batch_heuristic_multiplier",
     "ufm_set_sensor", "ufm_set_survey", "ufm_set_survey_device", "ufm_reveal", "ufm_read_survey",
     "ufm_batch_set_sensor", "ufm_batch_set_survey", "ufm_batch_set_survey_device", "ufm_batch_reveal", "ufm_batch_read_survey",
+    "ufm_gaussian_taps", "ufm_set_image", "ufm_set_image_device", "ufm_batch_set_image", "ufm_batch_set_image_device",
 ]
 
 
@@ -185,6 +186,11 @@ def load_library():
     L.ufm_batch_set_survey_device.argtypes = [vp, i, vp, i, i]
     L.ufm_batch_reveal.argtypes = [vp, vp, vp]
     L.ufm_batch_read_survey.argtypes = [vp, i, vp]
+    L.ufm_gaussian_taps.argtypes = [i, vp]
+    L.ufm_set_image.argtypes = [vp, vp, i, i, vp, i, i]
+    L.ufm_set_image_device.argtypes = [vp, vp, i, i, vp, i, i]
+    L.ufm_batch_set_image.argtypes = [vp, i, vp, i, i, vp, i, i]
+    L.ufm_batch_set_image_device.argtypes = [vp, i, vp, i, i, vp, i, i]
     _LIB = L
     return L
 
@@ -233,6 +239,29 @@ def _survey_args(raster, width=None, length=None):
     if raster.ndim != 2:
         raise UfmError("a survey is a matrix")
     return raster.ctypes.data, raster.shape[1], raster.shape[0], False, raster
+
+
+def gaussian_taps(ksize):
+    """ufm_gaussian_taps: the taps cv2.GaussianBlur(img, (k, k), 0) applies to 8-bit images (uint16 [ksize], their sum 256) -- the C
+    definition of harness.gaussian_kernel_fixed; ksize odd, 1 .. 31"""
+    ksize = int(ksize)
+    taps = np.zeros(max(ksize, 1), np.uint16)
+    _chk(load_library().ufm_gaussian_taps(ksize, taps.ctypes.data), "ufm_gaussian_taps")
+    return taps
+
+
+def _image_args(img, taps, ksize, width, length):
+    """(pointer, width, length, on_device, taps uint16, the object to keep alive) of a bitmap for set_image: the image as a survey is taken
+    (_survey_args); the filter as `taps`, or as the Gaussian of `ksize`, or -- neither given -- {256}, no blur"""
+    if taps is not None and ksize is not None:
+        raise UfmError("set_image takes taps or ksize, not both")
+    if taps is None:
+        taps = gaussian_taps(1 if ksize is None else ksize)
+    taps = np.ascontiguousarray(taps)
+    if taps.ndim != 1 or taps.size == 0 or (taps < 0).any() or (taps > 65535).any():
+        raise UfmError("taps are a vector of uint16")
+    ptr, width, length, dev, keep = _survey_args(img, width, length)
+    return ptr, width, length, dev, taps.astype(np.uint16), keep
 
 
 def _read_census(call, what):
@@ -468,6 +497,14 @@ class Planner:
         _chk(self.L.ufm_read_survey(self.h, m.ctypes.data), "ufm_read_survey")
         return m
 
+    def set_image(self, img, taps=None, penalty=0, ksize=None, width=None, length=None):
+        """ufm_set_image / _device: the grey-scale bitmap becomes the map (blurred by `taps` -- or gaussian_taps(ksize) --, complemented,
+        0 -> 1, + penalty saturating) and its survey (complemented, 0 -> 1) in one launch: harness.simulation_data on the device.  A host
+        matrix, or a device buffer (.ptr) with width and length"""
+        ptr, width, length, dev, taps, keep = _image_args(img, taps, ksize, width, length)
+        fn = self.L.ufm_set_image_device if dev else self.L.ufm_set_image
+        _chk(fn(self.h, ptr, width, length, taps.ctypes.data, len(taps), int(penalty)), "ufm_set_image")
+
     def check_layout(self):
         """(ring entries, cost-window bytes) that differ from the values they copy; (0, 0) when sound"""
         bad = (C.c_uint64 * 2)()
@@ -627,6 +664,13 @@ class BatchPlanner:
         m = np.empty((length, width), dtype=np.uint8)
         _chk(self.L.ufm_batch_read_survey(self.h, int(i), m.ctypes.data), "ufm_batch_read_survey")
         return m
+
+    def set_image(self, i, img, taps=None, penalty=0, ksize=None, width=None, length=None):
+        """as Planner.set_image, for map i"""
+        ptr, width, length, dev, taps, keep = _image_args(img, taps, ksize, width, length)
+        fn = self.L.ufm_batch_set_image_device if dev else self.L.ufm_batch_set_image
+        _chk(fn(self.h, int(i), ptr, width, length, taps.ctypes.data, len(taps), int(penalty)), "ufm_batch_set_image")
+        self._dims = (length + (0 if self.algo == ALGO_DFM else 1), width + (0 if self.algo == ALGO_DFM else 1))
 
     def set_start(self, i, x, y):
         _chk(self.L.ufm_batch_set_start(self.h, i, float(x), float(y)), "ufm_batch_set_start")

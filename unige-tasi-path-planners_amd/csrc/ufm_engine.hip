@@ -50,6 +50,7 @@ namespace {
 #include "ufm_cspace.h"
 #include "ufm_census.h"
 #include "ufm_sensor.h"
+#include "ufm_prepare.h"
 
 #include "ufm_host.h"
 #include "ufm_delta.h"
@@ -328,6 +329,13 @@ int ufm_reveal(ufm_t *p, int row, int col, uint64_t *changed) {
     { int rc = p->e->reveal(c); if (rc != UFM_OK) return rc; }
     return changed ? p->e->reveal_counts(c, changed) : UFM_OK;
 }
+int ufm_gaussian_taps(int ksize, uint16_t *taps) { return prep_gaussian_taps(ksize, taps) ? UFM_OK : UFM_ERR_INVALID; }
+int ufm_set_image(ufm_t *p, const uint8_t *host_image, int width, int length, const uint16_t *taps, int ntaps, int penalty) {
+    return p ? engine_set_image(p->e, 0, host_image, false, width, length, taps, ntaps, penalty) : UFM_ERR_INVALID;
+}
+int ufm_set_image_device(ufm_t *p, const uint8_t *dev_image, int width, int length, const uint16_t *taps, int ntaps, int penalty) {
+    return p ? engine_set_image(p->e, 0, dev_image, true, width, length, taps, ntaps, penalty) : UFM_ERR_INVALID;
+}
 int ufm_set_profiling(ufm_t *p, int enable) { if (!p) return UFM_ERR_INVALID; p->e->profiling = enable != 0; return UFM_OK; }
 void *ufm_stream(ufm_t *p) { return p ? (void *)p->e->stream : nullptr; }
 
@@ -479,6 +487,14 @@ int ufm_batch_set_sensor(ufm_batch_t *b, const uint8_t *mask, int mw, int mh, in
 }
 int ufm_batch_set_survey(ufm_batch_t *b, int i, const uint8_t *host_survey, int width, int length) { UFM_BATCH_MAP(b, i); return engine_set_survey(e, li, host_survey, false, width, length); }
 int ufm_batch_set_survey_device(ufm_batch_t *b, int i, const uint8_t *dev_survey, int width, int length) { UFM_BATCH_MAP(b, i); return engine_set_survey(e, li, dev_survey, true, width, length); }
+int ufm_batch_set_image(ufm_batch_t *b, int i, const uint8_t *host_image, int width, int length, const uint16_t *taps, int ntaps, int penalty) {
+    UFM_BATCH_MAP(b, i);
+    return engine_set_image(e, li, host_image, false, width, length, taps, ntaps, penalty);
+}
+int ufm_batch_set_image_device(ufm_batch_t *b, int i, const uint8_t *dev_image, int width, int length, const uint16_t *taps, int ntaps, int penalty) {
+    UFM_BATCH_MAP(b, i);
+    return engine_set_image(e, li, dev_image, true, width, length, taps, ntaps, penalty);
+}
 int ufm_batch_read_survey(ufm_batch_t *b, int i, uint8_t *host_survey) { UFM_BATCH_MAP(b, i); return engine_read_survey(e, li, host_survey); }
 // The maps grouped by the device that owns them (contiguous blocks: a shard's centres are a slice of the caller's array): every shard is
 // checked before any of them launches; then one k_reveal per shard, queued side by side, and only then the counts are waited for.
@@ -521,6 +537,10 @@ int ufm_batch_track_changes(ufm_batch_t *b, int enable) {
 int ufm_batch_read_changes(ufm_batch_t *b, int i, int cap, int32_t *xy, float *g, int32_t *info, int *total) { UFM_BATCH_MAP(b, i); return engine_read_changes(e, li, cap, xy, g, info, total); }
 // profiling: duration of the last scan kernel of ufm_read_changes (tools/delta_probe.py; not part of include/ufm.h)
 int ufm_debug_delta_ms(ufm_t *p, float *ms) { if (!p || !ms) return UFM_ERR_INVALID; *ms = p->e->trk_scan_ms; return UFM_OK; }
+// profiling: duration of the last k_prepare of ufm_set_image / of map i's ufm_batch_set_image, taken from the dispatch while
+// ufm_set_profiling is on (tools/prepare_probe.py; not part of include/ufm.h)
+int ufm_debug_prepare_ms(ufm_t *p, float *ms) { if (!p || !ms) return UFM_ERR_INVALID; *ms = p->e->prep_ms; return UFM_OK; }
+int ufm_debug_batch_prepare_ms(ufm_batch_t *b, int i, float *ms) { UFM_BATCH_MAP(b, i); if (!ms) return UFM_ERR_INVALID; *ms = e->prep_ms; return UFM_OK; }
 int ufm_extract_path(ufm_t *p, int max_steps, int lookahead, int allow_indirect,
                      float *path_xy, int cap_points, float *step_costs, int cap_costs, ufm_path_info *info) {
     return p ? engine_extract_path(p->e, max_steps, lookahead, allow_indirect, path_xy, cap_points, step_costs, cap_costs, info) : UFM_ERR_INVALID;

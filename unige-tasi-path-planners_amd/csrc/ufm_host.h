@@ -296,6 +296,13 @@ struct Engine {
     int reveal_check(const int32_t *centres) const;
     int reveal(const int32_t *centres);
     int reveal_counts(const int32_t *centres, uint64_t *changed);
+    // Map preparation (ufm_set_image; ufm_prepare.h).  Never called -- the default -- nothing below exists.  k_prepare must not
+    // read what it writes: a host bitmap, or a device bitmap that overlaps the rasters, goes through this buffer, which is the engine's and
+    // reused by every map, not kept per map.
+    uint8_t *d_image = nullptr;
+    size_t d_image_cap = 0;
+    hipEvent_t prep_ev[2] = {nullptr, nullptr};   // profiling: on the k_prepare dispatch itself
+    float prep_ms = 0.0f;            // ... its duration (tools/prepare_probe.py)
     // step deltas (ufm_track_changes / ufm_read_changes, ufm_delta.h): nothing below exists unless a caller turned tracking on
     bool track = false;
     float *trk_g = nullptr;          // the baseline: the field as the caller was last told, in the layout of P.G (same gstride)
@@ -1418,8 +1425,9 @@ int engine_destroy(Engine *e) {
     for (hipEvent_t v : e->own_ev) if (v) hipEventDestroy(v);
     for (hipEvent_t v : e->reg_ev) if (v) hipEventDestroy(v);
     for (hipEvent_t v : e->trk_ev) if (v) hipEventDestroy(v);
+    for (hipEvent_t v : e->prep_ev) if (v) hipEventDestroy(v);
     e->census_free();
-    free_all(hipFree, e->d_sensor, e->d_reveal, e->d_reveal_cnt);
+    free_all(hipFree, e->d_sensor, e->d_reveal, e->d_reveal_cnt, e->d_image);
     free_all(hipHostFree, e->h_centres);
     free_all(hipFree, e->d_cs_patch, e->d_patch, e->d_pmask, e->d_field, e->d_info, e->d_jobs, e->d_path);
     free_all(hipHostFree, e->h_jobs, e->h_path, e->h_patch, e->h_lazy);
@@ -1430,8 +1438,11 @@ int engine_destroy(Engine *e) {
     return UFM_OK;
 }
 
-int engine_set_map(Engine *e, int m, const uint8_t *src, bool on_device, int width, int length) {
-    if (!e || !src || m < 0 || m >= e->nmaps || width <= 0 || length <= 0) return UFM_ERR_INVALID;
+// What ufm_set_map* and ufm_set_image* share: map m gets a new raster of width x length.  fill(dst) queues whatever writes the caller's
+// raster to dst -- map m's slot of the raw store with a footprint, of the planning raster without -- and does everything of its own that
+// can fail before its first write; the rest is the same for both: held patches first, (re)allocation under the batch's one-size rule,
+// the dilation, the census, the cost windows, the mean traversable cost, an empty step-delta baseline, the goal's validity.
+template <class Fill> int engine_new_raster(Engine *e, int m, int width, int length, Fill &&fill) {
     HIPCHK(hipSetDevice(e->device));
     if (e->allocated) { int rc = e->flush_deferred(); if (rc != UFM_OK) return rc; }   // (patches held back belong before the new raster)
     if (!e->allocated || width != e->W || length != e->L) {
@@ -1443,8 +1454,7 @@ int engine_set_map(Engine *e, int m, const uint8_t *src, bool on_device, int wid
         if (e->census_on) HIPCHK(hipMemsetAsync(e->d_census, 0, sizeof(uint32_t) * CENSUS_BINS * e->nmaps, e->stream));   // (no map has a raster)
     }
     // (a footprint: the input is the raw raster -- kept, and dilated into the planning raster before anything reads that one)
-    HIPCHK(hipMemcpyAsync((e->cs.on ? e->d_raw : e->P.cost) + (size_t)m * e->P.cstride, src, (size_t)width * length,
-                          on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, e->stream));
+    { int rc = fill((e->cs.on ? e->d_raw : e->P.cost) + (size_t)m * e->P.cstride); if (rc != UFM_OK) return rc; }
     if (e->cs.on) e->cspace_dilate(m, e->P.cost + (size_t)m * e->P.cstride, width, PatchRect{m, 0, 0, width, length});
     if (e->census_on) { e->census_build(m); e->census_publish(); }      // (the planning raster is final; published by the wait below)
     k_cost_windows<<<2048, 256, 0, e->stream>>>(e->P, m);
@@ -1462,6 +1472,55 @@ int engine_set_map(Engine *e, int m, const uint8_t *src, bool on_device, int wid
     // goal element validity depends on the map size
     MapState &ms = e->maps[m];
     if (ms.goal_set) ms.goal_elem_valid = ms.goal_ex >= 0 && ms.goal_ey >= 0 && ms.goal_ex < e->P.EX && ms.goal_ey < e->P.EY;
+    return UFM_OK;
+}
+
+int engine_set_map(Engine *e, int m, const uint8_t *src, bool on_device, int width, int length) {
+    if (!e || !src || m < 0 || m >= e->nmaps || width <= 0 || length <= 0) return UFM_ERR_INVALID;
+    return engine_new_raster(e, m, width, length, [&](uint8_t *dst) -> int {
+        HIPCHK(hipMemcpyAsync(dst, src, (size_t)width * length, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, e->stream));
+        return UFM_OK;
+    });
+}
+
+// ufm_set_image* / ufm_batch_set_image*: the bitmap becomes map m's raster AND its survey (k_prepare, one launch).  The survey's array and
+// the staging buffer are seen to before k_prepare writes either raster; the wait at the end of engine_new_raster() is what frees the
+// caller's buffer -- and the staging buffer for the next map.
+int engine_set_image(Engine *e, int m, const uint8_t *src, bool on_device, int width, int length, const uint16_t *taps, int ntaps, int penalty) {
+    PrepTaps k;
+    if (!e || !src || m < 0 || m >= e->nmaps || !prep_args_valid(taps, ntaps, width, length, penalty) || !prep_pack(taps, ntaps, &k)) return UFM_ERR_INVALID;
+    if (e->allocated && (width != e->W || length != e->L))       // (the one-size rule of a batch, before anything is flushed or freed)
+        for (int j = 0; j < e->nmaps; ++j) if (j != m && e->maps[j].have_map) return UFM_ERR_INVALID;
+    bool timed = false;
+    const int rc = engine_new_raster(e, m, width, length, [&](uint8_t *dst) -> int {
+        const size_t n = (size_t)width * length, all = e->P.cstride * e->nmaps;
+        if (!e->d_survey) {
+            if (hipMalloc(&e->d_survey, all) != hipSuccess) { (void)hipGetLastError(); e->d_survey = nullptr; return UFM_ERR_NOMEM; }
+            e->have_survey.assign((size_t)e->nmaps, 0);
+        }
+        const uint8_t *image = src;
+        if (!on_device || prep_overlap(src, n, e->P.cost, all) || prep_overlap(src, n, e->d_survey, all) || (e->cs.on && prep_overlap(src, n, e->d_raw, all))) {
+            if (n > e->d_image_cap) { int rc2 = regrow(e->stream, n, e->d_image_cap, n, e->d_image); if (rc2 != UFM_OK) return rc2; }
+            HIPCHK(hipMemcpyAsync(e->d_image, src, n, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, e->stream));
+            image = e->d_image;
+        }
+        PrepareJob j{};
+        j.src = image; j.out_l = dst; j.out_h = e->d_survey + (size_t)m * e->P.cstride;
+        j.W = width; j.L = length; j.penalty = penalty;
+        j.wide_in = width % 4 == 0 && prep_aligned4(j.src);
+        j.wide_out = width % 4 == 0 && prep_aligned4(j.out_l) && prep_aligned4(j.out_h);
+        j.taps = k;
+        timed = e->profiling;
+        if (timed && !e->prep_ev[0]) { HIPCHK(hipEventCreate(&e->prep_ev[0])); HIPCHK(hipEventCreate(&e->prep_ev[1])); }
+        launch(k_prepare, dim3(prep_grid_x(width), prep_grid_y(length)), dim3(PREP_THREADS), e->stream, timed ? e->prep_ev[0] : nullptr,
+               timed ? e->prep_ev[1] : nullptr, j);
+        HIPCHK(hipGetLastError());
+        e->have_survey[m] = 1;
+        return UFM_OK;
+    });
+    if (rc != UFM_OK) return rc;
+    e->reveal_busy = false;                  // (the call has waited for the stream)
+    if (timed) HIPCHK(hipEventElapsedTime(&e->prep_ms, e->prep_ev[0], e->prep_ev[1]));
     return UFM_OK;
 }
 

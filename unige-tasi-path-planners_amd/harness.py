@@ -166,7 +166,8 @@ class Pipes:
 
 def run_mission(cmd, pipe_to_planner, pipe_from_planner, img_h, start, goal, radius=5, cspace_diameter=1,
                 low_res_penalty=10, use_heuristic=False, max_moves=10000, on_map=None, on_move=None, display_shift=0.0,
-                append_pipes=True, tof=False, on_expanded=None, planner_inflates=False, planner_min_cost=False, planner_senses=False):
+                append_pipes=True, tof=False, on_expanded=None, planner_inflates=False, planner_min_cost=False, planner_senses=False,
+                planner_prepares=False, filter_size=3):
     """One mission as Tests/run_test.py:85-177 runs it: launch the planner process `cmd`, send the
     C-space of the low-resolution map, then per robot position reveal the disc of radius `radius`,
     send its bounding patch and the heuristic hint, receive the planned path.  start / goal are
@@ -182,7 +183,15 @@ def run_mission(cmd, pipe_to_planner, pipe_from_planner, img_h, start, goal, rad
     placeholder, int(data_l.min()) -- and together with planner_inflates nothing is dilated here at all.
     planner_senses: the planner process uncovers the field of view itself (ufm_planner --sense R with R = radius): the high-resolution data
     goes out ONCE, directly after the map, and every move's patch message is empty (h = w = 0, no bytes); the harness still keeps its own
-    low-resolution map up to date, so on_move reports the patch the reference would have sent.  Returns the list of positions visited and whether the planner reported the end."""
+    low-resolution map up to date, so on_move reports the patch the reference would have sent.
+    filter_size: the Gaussian's size in simulation_data (run_test.py: 3, run_simulator.py: 13).
+    planner_prepares: the planner process makes the map from the bitmap itself (ufm_planner --image K P with K = filter_size and
+    P = low_res_penalty): where the map raster would go, the grey-scale bitmap img_h goes out, framed the same way, and with
+    planner_senses no survey message follows it -- the planner has made that too.  The low-resolution map is then the planner's to
+    inflate: a cspace_diameter above 1 needs planner_inflates.  on_map still gets the map the reference would have sent.
+    Returns the list of positions visited and whether the planner reported the end."""
+    if planner_prepares and cspace_diameter > 1 and not planner_inflates:
+        raise ValueError("planner_prepares: the planner makes the raw map, so it must inflate it too (planner_inflates)")
     for p in (pipe_to_planner, pipe_from_planner):
         if not os.path.exists(p):
             os.mkfifo(p)
@@ -195,14 +204,17 @@ def run_mission(cmd, pipe_to_planner, pipe_from_planner, img_h, start, goal, rad
         io = Pipes(pipe_to_planner, pipe_from_planner, alive=lambda: proc.poll() is None)
         assert io.recv("b") == (0,)
         io.send("b", 0)
-        data_l, data_h = simulation_data(img_h, low_res_penalty)
+        data_l, data_h = simulation_data(img_h, low_res_penalty, filter_size)
         host_inflates = not (planner_inflates and planner_min_cost)
         cspace = dilate(data_l, cspace_diameter) if host_inflates else data_l
         min_cost = int(data_l.min()) if planner_min_cost else int(cspace.min())
         height, width = cspace.shape
         io.send("ii", width, height)
-        io.send_bytes(np.ascontiguousarray(data_l if planner_inflates else cspace).tobytes())
-        if planner_senses:
+        if planner_prepares:
+            io.send_bytes(np.ascontiguousarray(img_h, dtype=np.uint8).tobytes())
+        else:
+            io.send_bytes(np.ascontiguousarray(data_l if planner_inflates else cspace).tobytes())
+        if planner_senses and not planner_prepares:
             io.send_bytes(np.ascontiguousarray(data_h).tobytes())
         if start is not None:
             io.send("ffffB", float(start[0]), float(start[1]), float(goal[0]), float(goal[1]), 1 if tof else 0)

@@ -114,6 +114,18 @@ class ReplannerBase {
     map.set_dims(nx, ny);
     initialize_graph = false;
   }
+  /** Map preparation on the device (ufm_set_image; no reference counterpart: the reference's simulator blurs, complements and penalises the
+   *  bitmap on the host, run_simulator.py:106-113,148): in place of set_map, the grey-scale bitmap with the taps of one axis
+   *  (ufm_gaussian_taps) and the penalty; the engine makes the map and its survey from it, so no set_survey follows.  `grid` then holds
+   *  the BITMAP the host handed over -- its size, start and goal are right, its bytes are not costs. */
+  void set_image(const std::shared_ptr<uint8_t> &image, int w, int h, const uint16_t *taps, int ntaps, int penalty) {
+    grid.init(image, w, h);
+    check(ufm_set_image(handle_, image.get(), w, h, taps, ntaps, penalty));
+    int nx = 0, ny = 0;
+    check(ufm_field_dims(handle_, &nx, &ny));
+    map.set_dims(nx, ny);
+    initialize_graph = false;
+  }
   void patch_map(const std::shared_ptr<uint8_t> &patch, int x, int y, int w, int h) {
     grid.update(patch, x, y, w, h);
     check(ufm_patch_map(handle_, patch.get(), x, y, w, h));
