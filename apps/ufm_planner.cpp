@@ -12,7 +12,7 @@
 // LinearInterpolationPathExtractor, reset / set_* / patch_map / step / extract_path, u_time,
 // p_time, e_time, map.size(), map.buckets.
 //
-//   ufm_planner [--planner FD|SG|DFM] [--level K] [--max-moves N] [--verify-follow] [--inflate D] [--auto-heuristic] [--sense R] [--image K P] <fifo_in> <fifo_out>
+//   ufm_planner [--planner FD|SG|DFM] [--level K] [--max-moves N] [--verify-follow] [--inflate D] [--auto-heuristic] [--sense R] [--image K P] [--layers N] <fifo_in> <fifo_out>
 //        start, goal and the `tof` flag arrive in-band after the map (DFM/main.cpp:62-67)
 //   ufm_planner [...] <mapfile> <from_x> <from_y> <to_x> <to_y> <cspace> <fifo_in> <fifo_out> <gui> <tof> <outpath>
 //        the 11-argument form of FDSTAR/main.cpp:16-31 and SGDFM/main.cpp
@@ -32,6 +32,11 @@
 // 1 .. 31, complements it and adds the saturating penalty P, 0 .. 255 -- the simulator's simulation_data (run_simulator.py:106-113,148) --
 // and the same launch leaves the complemented bitmap as the survey: with --sense R no separate survey message is sent.  Composes with
 // --inflate and --auto-heuristic: the simulator then hands over a bitmap and positions, nothing else.
+// --layers N: the map is the maximum of N cost layers the engine keeps (ufm_set_layers), N = 2 .. 4; needs --sense.  Layer 0 is the map as
+// it arrives (or as --image makes it) with its survey; behind the map message and the survey message (the latter absent with --image)
+// N - 1 more rasters of width x height bytes follow on the wire: the surveys of layers 1 .. N - 1, whose known layers start at zero
+// (rock_aboundance_l = np.zeros(...), Tests/run_test.py:102).  Every move then uncovers the disc in all N layers with one reveal.
+// Composes with --inflate, --auto-heuristic and --image.
 // With `tof` the expanded-element dump after every step is kept up to date from the steps' deltas (ExpandedMap::follow_changes), not
 // read back whole; --verify-follow also builds it the old way every step -- a read of the whole field through a second view of the
 // same planner -- and ends the run (exit code 3) if the two differ in any element, value, Info or order.
@@ -94,6 +99,7 @@ struct Options {
   int sense = -1;            // --sense R: radius of the field of view the planner uncovers itself (< 0: off)
   int image = 0;             // --image K P: the wire carries the bitmap, blurred here with K Gaussian taps (0: off) ...
   int image_penalty = 0;     // ... and P added, saturating
+  int layers = 1;            // --layers N: cost layers of the engine; the surveys of layers 1 .. N - 1 follow the survey on the wire
   std::string fifo_in, fifo_out;
 };
 
@@ -116,6 +122,11 @@ int serve(Options opt, bool cell_planner, bool indirect) {
   if (opt.sense >= 0 && !opt.image) {
     survey = byte_block((size_t)width * height);
     io.get_bytes(survey.get(), (size_t)width * height);
+  }
+  std::vector<std::shared_ptr<uint8_t>> layer_surveys;
+  for (int k = 1; k < opt.layers; ++k) {
+    layer_surveys.push_back(byte_block((size_t)width * height));
+    io.get_bytes(layer_surveys.back().get(), (size_t)width * height);
   }
   if (opt.inband) {
     opt.from_x = io.get<float>(); opt.from_y = io.get<float>();
@@ -143,6 +154,7 @@ int serve(Options opt, bool cell_planner, bool indirect) {
         disc[(size_t)a * n + b] = (double)((b - r) * (b - r)) / (double)(r * r) + (double)((a - r) * (a - r)) / (double)(r * r) <= 1.0;
     planner.set_cspace(disc.data(), n, n);
   }
+  if (opt.layers > 1 && planner.set_layers(opt.layers) != UFM_OK) throw std::runtime_error("--layers: N is 1 .. " + std::to_string(UFM_MAX_LAYERS));
   if (opt.image) {
     uint16_t taps[31];
     if (ufm_gaussian_taps(opt.image, taps) != UFM_OK) throw std::runtime_error("--image: K is odd, 1 .. 31");
@@ -173,6 +185,9 @@ int serve(Options opt, bool cell_planner, bool indirect) {
       for (int b = 0; b < fov_n; ++b) fov[(size_t)a * fov_n + b] = (a - r) * (a - r) + (b - r) * (b - r) <= r * r;
     if (!opt.image) planner.set_survey(survey, width, height);        // (--image: set_image has left the survey)
     if (planner.last_error != UFM_OK) throw std::runtime_error("set_survey failed with " + std::to_string(planner.last_error));
+    for (int k = 1; k < opt.layers; ++k)
+      if (planner.set_layer_survey(k, layer_surveys[(size_t)k - 1], width, height) != UFM_OK)
+        throw std::runtime_error("set_layer_survey failed with " + std::to_string(planner.last_error));
   }
   // the dump after every step: follow the steps' deltas on the host instead of reading the whole field back each time
   if (opt.tof && planner.map.follow_changes(true) != UFM_OK) throw std::runtime_error("follow_changes failed");
@@ -253,7 +268,7 @@ int serve(Options opt, bool cell_planner, bool indirect) {
 
 void usage(const char *argv0) {
   std::fprintf(stderr,
-               "Usage:\n\t%s [--planner FD|SG|DFM] [--level K] [--max-moves N] [--verify-follow] [--inflate D] [--auto-heuristic] [--sense R] [--image K P] <fifo_in> <fifo_out>\n"
+               "Usage:\n\t%s [--planner FD|SG|DFM] [--level K] [--max-moves N] [--verify-follow] [--inflate D] [--auto-heuristic] [--sense R] [--image K P] [--layers N] <fifo_in> <fifo_out>\n"
                "\t%s [...] <mapfile> <from_x> <from_y> <to_x> <to_y> <cspace> <fifo_in> <fifo_out> <gui> <tof> <outpath>\n",
                argv0, argv0);
 }
@@ -287,8 +302,14 @@ int main(int argc, char **argv) {
     else if (a == "--auto-heuristic") opt.auto_heuristic = true;
     else if (a == "--sense" && i + 1 < argc) opt.sense = std::atoi(argv[++i]);
     else if (a == "--image" && i + 2 < argc) { opt.image = std::atoi(argv[++i]); opt.image_penalty = std::atoi(argv[++i]); }
+    else if (a == "--layers" && i + 1 < argc) opt.layers = std::atoi(argv[++i]);
     else if (a == "-h" || a == "--help") { usage(argv[0]); return 0; }
     else pos.push_back(a);
+  }
+  if (opt.layers != 1 && (opt.sense < 0 || opt.layers < 1 || opt.layers > UFM_MAX_LAYERS)) {
+    std::fprintf(stderr, "--layers N needs --sense R, N = 1 .. %d\n", UFM_MAX_LAYERS);
+    usage(argv[0]);
+    return 1;
   }
   try {
     if (pos.size() == 2) {

@@ -368,6 +368,53 @@ int ufm_gaussian_taps(int ksize, uint16_t *taps);
 int ufm_set_image(ufm_t *p, const uint8_t *host_image, int width, int length, const uint16_t *taps, int ntaps, int penalty);
 int ufm_set_image_device(ufm_t *p, const uint8_t *dev_image, int width, int length, const uint16_t *taps, int ntaps, int penalty);
 
+/* ---- cost layers: the map is the maximum of several rasters.  The reference's simulator keeps TWO known rasters, each with a
+ * high-resolution counterpart -- slope (data_l / data_h) and rocks (rock_aboundance_l / rock_aboundance_h), Tests/run_test.py:102 --,
+ * uncovers the same disc in both (round_patch_update twice) and plans on dilate(np.maximum(data_l, rock_aboundance_l)),
+ * Tests/run_test.py:136-140.  Here the layers lie in device memory next to the map and the engine keeps the maximum.  OPT-IN: with one
+ * layer -- the default -- nothing is allocated, nothing is launched and no route differs.
+ * INVARIANT.  A handle has n layers, 1 <= n <= UFM_MAX_LAYERS.  With n > 1 the engine keeps a store layer[k][map][length][width],
+ * k = 0 .. n-1, and between any two calls of this header
+ *     the caller's raster == max over k of layer[k], cell for cell,
+ * the caller's raster being what the patch route is handed today: the RAW raster when a footprint is set, the planning raster
+ * otherwise.  Everything downstream sees only that raster and is unchanged: dilation, census, seeding, the replan's block kernel, step
+ * deltas, ufm_read_map, ufm_read_raw_map.
+ * ufm_set_layers(p, n): a property of the handle, like the footprint -- set after ufm_create and before the first ufm_set_map* /
+ * ufm_set_image*, UFM_ERR_INVALID otherwise.  n = 1 is "off".
+ * ufm_set_map* / ufm_set_image* with n > 1 feed layer 0 and zero layers 1 .. n-1 (rock_aboundance_l = np.zeros(...)): after the call
+ * the caller's raster equals the argument, exactly as today.  The surveys of all layers follow the survey rule: kept if the dimensions
+ * are unchanged, dropped otherwise; ufm_set_image replaces survey 0 only; ufm_reset leaves layers and surveys alone.
+ * ufm_patch_layer(p, k, patch, x, y, w, h) / _device, 0 <= k < n, defined by equivalence.  The bytes go into layer k's store over the
+ * rectangle (rows x .. x+h-1, columns y .. y+w-1, as ufm_patch_map's); let C be the dense maximum of all layers over that rectangle
+ * after the store.  The call leaves the handle in exactly the state ufm_patch_map_device(p, C, x, y, w, h) would.  ufm_patch_map* with
+ * n > 1 is ufm_patch_layer(p, 0, ...).  The patch is read at the call, stream-ordered.  DECLINED while n > 1, exactly as with a
+ * footprint or the census: the two routes that apply a patch later than the call -- a single planner's held small host patches and a
+ * batch's "defer_patches", which is accepted and WITHOUT EFFECT.  Both would put one layer's bytes into the composed raster.
+ * ufm_set_layer(p, k, raster, width, length) / _device: layer k wholesale, defined as ufm_patch_layer(p, k, raster, 0, 0, width, length),
+ * a whole-map patch.  It is NOT a set_map: the field is kept and the next step replans.  The dimensions must equal the map's.
+ * ufm_set_layer_survey(p, k, survey, width, length) / _device: the survey of layer k; k = 0 is ufm_set_survey (also with n = 1).
+ * ufm_read_layer / ufm_read_layer_survey copy layer k / its survey back, [length][width]; UFM_ERR_INVALID when n == 1 or the survey is
+ * not set.
+ * ufm_reveal with n > 1.  R and the mask's coverage as above.  For every layer k that has a survey new_k = survey_k where the mask
+ * covers a cell and layer_k elsewhere; layers without a survey are unchanged; Q = max over k of new_k, over R.  The call stores new_k
+ * into the layer stores and then leaves the handle exactly as ufm_patch_map_device(p, Q, R) would.  changed: the number of cells of the
+ * caller's raster -- the composed one -- whose byte changed.  At least one layer must have a survey, UFM_ERR_INVALID otherwise.  One
+ * launch serves all layers of all maps of an engine; the work is proportional to n |R|, never to the map.
+ * UFM_ERR_INVALID, before anything is launched, allocated or written, the handle staying usable: a NULL handle or buffer; n outside
+ * 1 .. UFM_MAX_LAYERS, or ufm_set_layers after a map is set; k outside 0 .. n-1, or any layer call with n == 1 (except
+ * ufm_set_layer_survey(p, 0, ...)); dimensions that differ from the map's, or a layer for a map without a raster; a rectangle outside
+ * the map. ---- */
+#define UFM_MAX_LAYERS 4
+int ufm_set_layers(ufm_t *p, int n);
+int ufm_patch_layer(ufm_t *p, int k, const uint8_t *host_patch, int x, int y, int w, int h);
+int ufm_patch_layer_device(ufm_t *p, int k, const uint8_t *dev_patch, int x, int y, int w, int h);
+int ufm_set_layer(ufm_t *p, int k, const uint8_t *host_raster, int width, int length);
+int ufm_set_layer_device(ufm_t *p, int k, const uint8_t *dev_raster, int width, int length);
+int ufm_set_layer_survey(ufm_t *p, int k, const uint8_t *host_survey, int width, int length);
+int ufm_set_layer_survey_device(ufm_t *p, int k, const uint8_t *dev_survey, int width, int length);
+int ufm_read_layer(ufm_t *p, int k, uint8_t *host_raster);
+int ufm_read_layer_survey(ufm_t *p, int k, uint8_t *host_survey);
+
 /* ---- measurement hooks ---- */
 int ufm_set_profiling(ufm_t *p, int enable);   /* HIP-event timing of every relax launch */
 void *ufm_stream(ufm_t *p);                    /* hipStream_t the kernels run on */
@@ -442,6 +489,18 @@ int ufm_batch_read_survey(ufm_batch_t *b, int i, uint8_t *host_survey);
 int ufm_batch_set_image(ufm_batch_t *b, int i, const uint8_t *host_image, int width, int length, const uint16_t *taps, int ntaps, int penalty);
 int ufm_batch_set_image_device(ufm_batch_t *b, int i, const uint8_t *dev_image, int width, int length, const uint16_t *taps, int ntaps,
                                int penalty);
+/* as ufm_set_layers / ufm_patch_layer* / ufm_set_layer* / ufm_set_layer_survey* / ufm_read_layer / ufm_read_layer_survey: one n for every
+ * map on every shard, set before the first raster; layer k of map i.  ufm_batch_reveal stays one launch per engine, all layers of all
+ * its maps included. */
+int ufm_batch_set_layers(ufm_batch_t *b, int n);
+int ufm_batch_patch_layer(ufm_batch_t *b, int i, int k, const uint8_t *host_patch, int x, int y, int w, int h);
+int ufm_batch_patch_layer_device(ufm_batch_t *b, int i, int k, const uint8_t *dev_patch, int x, int y, int w, int h);
+int ufm_batch_set_layer(ufm_batch_t *b, int i, int k, const uint8_t *host_raster, int width, int length);
+int ufm_batch_set_layer_device(ufm_batch_t *b, int i, int k, const uint8_t *dev_raster, int width, int length);
+int ufm_batch_set_layer_survey(ufm_batch_t *b, int i, int k, const uint8_t *host_survey, int width, int length);
+int ufm_batch_set_layer_survey_device(ufm_batch_t *b, int i, int k, const uint8_t *dev_survey, int width, int length);
+int ufm_batch_read_layer(ufm_batch_t *b, int i, int k, uint8_t *host_raster);
+int ufm_batch_read_layer_survey(ufm_batch_t *b, int i, int k, uint8_t *host_survey);
 /* all maps in one launch: path_xy [n_maps][cap_points][2], step_costs [n_maps][cap_costs], info [n_maps] */
 int ufm_batch_extract_path(ufm_batch_t *b, int max_steps, int lookahead, int allow_indirect,
                            float *path_xy, int cap_points, float *step_costs, int cap_costs, ufm_path_info *info);

@@ -32,7 +32,12 @@ SYMBOLS = [
     "ufm_set_sensor", "ufm_set_survey", "ufm_set_survey_device", "ufm_reveal", "ufm_read_survey",
     "ufm_batch_set_sensor", "ufm_batch_set_survey", "ufm_batch_set_survey_device", "ufm_batch_reveal", "ufm_batch_read_survey",
     "ufm_gaussian_taps", "ufm_set_image", "ufm_set_image_device", "ufm_batch_set_image", "ufm_batch_set_image_device",
+    "ufm_set_layers", "ufm_patch_layer", "ufm_patch_layer_device", "ufm_set_layer", "ufm_set_layer_device",
+    "ufm_set_layer_survey", "ufm_set_layer_survey_device", "ufm_read_layer", "ufm_read_layer_survey",
+    "ufm_batch_set_layers", "ufm_batch_patch_layer", "ufm_batch_patch_layer_device", "ufm_batch_set_layer", "ufm_batch_set_layer_device",
+    "ufm_batch_set_layer_survey", "ufm_batch_set_layer_survey_device", "ufm_batch_read_layer", "ufm_batch_read_layer_survey",
 ]
+MAX_LAYERS = 4     # UFM_MAX_LAYERS
 
 
 class UfmError(RuntimeError):
@@ -191,6 +196,24 @@ def load_library():
     L.ufm_set_image_device.argtypes = [vp, vp, i, i, vp, i, i]
     L.ufm_batch_set_image.argtypes = [vp, i, vp, i, i, vp, i, i]
     L.ufm_batch_set_image_device.argtypes = [vp, i, vp, i, i, vp, i, i]
+    L.ufm_set_layers.argtypes = [vp, i]
+    L.ufm_patch_layer.argtypes = [vp, i, vp, i, i, i, i]
+    L.ufm_patch_layer_device.argtypes = [vp, i, vp, i, i, i, i]
+    L.ufm_set_layer.argtypes = [vp, i, vp, i, i]
+    L.ufm_set_layer_device.argtypes = [vp, i, vp, i, i]
+    L.ufm_set_layer_survey.argtypes = [vp, i, vp, i, i]
+    L.ufm_set_layer_survey_device.argtypes = [vp, i, vp, i, i]
+    L.ufm_read_layer.argtypes = [vp, i, vp]
+    L.ufm_read_layer_survey.argtypes = [vp, i, vp]
+    L.ufm_batch_set_layers.argtypes = [vp, i]
+    L.ufm_batch_patch_layer.argtypes = [vp, i, i, vp, i, i, i, i]
+    L.ufm_batch_patch_layer_device.argtypes = [vp, i, i, vp, i, i, i, i]
+    L.ufm_batch_set_layer.argtypes = [vp, i, i, vp, i, i]
+    L.ufm_batch_set_layer_device.argtypes = [vp, i, i, vp, i, i]
+    L.ufm_batch_set_layer_survey.argtypes = [vp, i, i, vp, i, i]
+    L.ufm_batch_set_layer_survey_device.argtypes = [vp, i, i, vp, i, i]
+    L.ufm_batch_read_layer.argtypes = [vp, i, i, vp]
+    L.ufm_batch_read_layer_survey.argtypes = [vp, i, i, vp]
     _LIB = L
     return L
 
@@ -505,6 +528,40 @@ class Planner:
         fn = self.L.ufm_set_image_device if dev else self.L.ufm_set_image
         _chk(fn(self.h, ptr, width, length, taps.ctypes.data, len(taps), int(penalty)), "ufm_set_image")
 
+    def set_layers(self, n):
+        """ufm_set_layers: n rasters per map whose element-wise maximum is the caller's raster (1: off, the default); before the first
+        set_map / set_image"""
+        _chk(self.L.ufm_set_layers(self.h, int(n)), "ufm_set_layers")
+
+    def patch_layer(self, k, patch, x, y, w=None, h=None):
+        """ufm_patch_layer / _device: the bytes into layer k over rows x .., columns y ..; the map takes the maximum over the layers there.
+        A host matrix, or a device buffer (.ptr) with w and h"""
+        ptr, w, h, dev, keep = _survey_args(patch, w, h)
+        fn = self.L.ufm_patch_layer_device if dev else self.L.ufm_patch_layer
+        _chk(fn(self.h, int(k), ptr, int(x), int(y), w, h), "ufm_patch_layer")
+
+    def set_layer(self, k, raster, width=None, length=None):
+        """ufm_set_layer / _device: layer k wholesale -- a whole-map patch, not a set_map: the field is kept"""
+        ptr, width, length, dev, keep = _survey_args(raster, width, length)
+        fn = self.L.ufm_set_layer_device if dev else self.L.ufm_set_layer
+        _chk(fn(self.h, int(k), ptr, width, length), "ufm_set_layer")
+
+    def set_layer_survey(self, k, raster, width=None, length=None):
+        """ufm_set_layer_survey / _device: what the sensor would see of layer k (k = 0: set_survey)"""
+        ptr, width, length, dev, keep = _survey_args(raster, width, length)
+        fn = self.L.ufm_set_layer_survey_device if dev else self.L.ufm_set_layer_survey
+        _chk(fn(self.h, int(k), ptr, width, length), "ufm_set_layer_survey")
+
+    def read_layer(self, k, width, length):
+        m = np.empty((length, width), dtype=np.uint8)
+        _chk(self.L.ufm_read_layer(self.h, int(k), m.ctypes.data), "ufm_read_layer")
+        return m
+
+    def read_layer_survey(self, k, width, length):
+        m = np.empty((length, width), dtype=np.uint8)
+        _chk(self.L.ufm_read_layer_survey(self.h, int(k), m.ctypes.data), "ufm_read_layer_survey")
+        return m
+
     def check_layout(self):
         """(ring entries, cost-window bytes) that differ from the values they copy; (0, 0) when sound"""
         bad = (C.c_uint64 * 2)()
@@ -671,6 +728,38 @@ class BatchPlanner:
         fn = self.L.ufm_batch_set_image_device if dev else self.L.ufm_batch_set_image
         _chk(fn(self.h, int(i), ptr, width, length, taps.ctypes.data, len(taps), int(penalty)), "ufm_batch_set_image")
         self._dims = (length + (0 if self.algo == ALGO_DFM else 1), width + (0 if self.algo == ALGO_DFM else 1))
+
+    def set_layers(self, n):
+        """as Planner.set_layers: one n for every map on every shard"""
+        _chk(self.L.ufm_batch_set_layers(self.h, int(n)), "ufm_batch_set_layers")
+
+    def patch_layer(self, i, k, patch, x, y, w=None, h=None):
+        """as Planner.patch_layer, for map i"""
+        ptr, w, h, dev, keep = _survey_args(patch, w, h)
+        fn = self.L.ufm_batch_patch_layer_device if dev else self.L.ufm_batch_patch_layer
+        _chk(fn(self.h, int(i), int(k), ptr, int(x), int(y), w, h), "ufm_batch_patch_layer")
+
+    def set_layer(self, i, k, raster, width=None, length=None):
+        """as Planner.set_layer, for map i"""
+        ptr, width, length, dev, keep = _survey_args(raster, width, length)
+        fn = self.L.ufm_batch_set_layer_device if dev else self.L.ufm_batch_set_layer
+        _chk(fn(self.h, int(i), int(k), ptr, width, length), "ufm_batch_set_layer")
+
+    def set_layer_survey(self, i, k, raster, width=None, length=None):
+        """as Planner.set_layer_survey, for map i"""
+        ptr, width, length, dev, keep = _survey_args(raster, width, length)
+        fn = self.L.ufm_batch_set_layer_survey_device if dev else self.L.ufm_batch_set_layer_survey
+        _chk(fn(self.h, int(i), int(k), ptr, width, length), "ufm_batch_set_layer_survey")
+
+    def read_layer(self, i, k, width, length):
+        m = np.empty((length, width), dtype=np.uint8)
+        _chk(self.L.ufm_batch_read_layer(self.h, int(i), int(k), m.ctypes.data), "ufm_batch_read_layer")
+        return m
+
+    def read_layer_survey(self, i, k, width, length):
+        m = np.empty((length, width), dtype=np.uint8)
+        _chk(self.L.ufm_batch_read_layer_survey(self.h, int(i), int(k), m.ctypes.data), "ufm_batch_read_layer_survey")
+        return m
 
     def set_start(self, i, x, y):
         _chk(self.L.ufm_batch_set_start(self.h, i, float(x), float(y)), "ufm_batch_set_start")

@@ -51,6 +51,7 @@ namespace {
 #include "ufm_census.h"
 #include "ufm_sensor.h"
 #include "ufm_prepare.h"
+#include "ufm_layers.h"
 
 #include "ufm_host.h"
 #include "ufm_delta.h"
@@ -336,6 +337,24 @@ int ufm_set_image(ufm_t *p, const uint8_t *host_image, int width, int length, co
 int ufm_set_image_device(ufm_t *p, const uint8_t *dev_image, int width, int length, const uint16_t *taps, int ntaps, int penalty) {
     return p ? engine_set_image(p->e, 0, dev_image, true, width, length, taps, ntaps, penalty) : UFM_ERR_INVALID;
 }
+int ufm_set_layers(ufm_t *p, int n) { return p ? engine_set_layers(p->e, n) : UFM_ERR_INVALID; }
+int ufm_patch_layer(ufm_t *p, int k, const uint8_t *host_patch, int x, int y, int w, int h) { return p ? engine_patch_layer(p->e, 0, k, host_patch, false, x, y, w, h) : UFM_ERR_INVALID; }
+int ufm_patch_layer_device(ufm_t *p, int k, const uint8_t *dev_patch, int x, int y, int w, int h) { return p ? engine_patch_layer(p->e, 0, k, dev_patch, true, x, y, w, h) : UFM_ERR_INVALID; }
+int ufm_set_layer(ufm_t *p, int k, const uint8_t *host_raster, int width, int length) { return p ? engine_set_layer(p->e, 0, k, host_raster, false, width, length) : UFM_ERR_INVALID; }
+int ufm_set_layer_device(ufm_t *p, int k, const uint8_t *dev_raster, int width, int length) { return p ? engine_set_layer(p->e, 0, k, dev_raster, true, width, length) : UFM_ERR_INVALID; }
+int ufm_set_layer_survey(ufm_t *p, int k, const uint8_t *host_survey, int width, int length) { return p ? engine_set_layer_survey(p->e, 0, k, host_survey, false, width, length) : UFM_ERR_INVALID; }
+int ufm_set_layer_survey_device(ufm_t *p, int k, const uint8_t *dev_survey, int width, int length) { return p ? engine_set_layer_survey(p->e, 0, k, dev_survey, true, width, length) : UFM_ERR_INVALID; }
+int ufm_read_layer(ufm_t *p, int k, uint8_t *host_raster) { return p ? engine_read_layer(p->e, 0, k, host_raster) : UFM_ERR_INVALID; }
+int ufm_read_layer_survey(ufm_t *p, int k, uint8_t *host_survey) { return p ? engine_read_layer_survey(p->e, 0, k, host_survey) : UFM_ERR_INVALID; }
+// profiling: duration of the last layer kernel (k_layer_compose / k_layer_compose_all / k_reveal_layers), taken from the dispatch while
+// ufm_set_profiling is on (tools/layers_probe.py; not part of include/ufm.h)
+int ufm_debug_layers_ms(ufm_t *p, float *ms) {
+    if (!p || !ms || !p->e->lay_timed) return UFM_ERR_INVALID;
+    HIPCHK(hipSetDevice(p->e->device));
+    HIPCHK(hipStreamSynchronize(p->e->stream));
+    HIPCHK(hipEventElapsedTime(ms, p->e->lay_ev[0], p->e->lay_ev[1]));
+    return UFM_OK;
+}
 int ufm_set_profiling(ufm_t *p, int enable) { if (!p) return UFM_ERR_INVALID; p->e->profiling = enable != 0; return UFM_OK; }
 void *ufm_stream(ufm_t *p) { return p ? (void *)p->e->stream : nullptr; }
 
@@ -496,6 +515,20 @@ int ufm_batch_set_image_device(ufm_batch_t *b, int i, const uint8_t *dev_image, 
     return engine_set_image(e, li, dev_image, true, width, length, taps, ntaps, penalty);
 }
 int ufm_batch_read_survey(ufm_batch_t *b, int i, uint8_t *host_survey) { UFM_BATCH_MAP(b, i); return engine_read_survey(e, li, host_survey); }
+int ufm_batch_set_layers(ufm_batch_t *b, int n) {
+    if (!b || b->shards.empty() || !layers_count_ok(n)) return UFM_ERR_INVALID;
+    for (Engine *e : b->shards) for (const MapState &ms : e->maps) if (ms.have_map) return UFM_ERR_INVALID;   // (all shards or none)
+    for (Engine *e : b->shards) { const int rc = engine_set_layers(e, n); if (rc != UFM_OK) return rc; }
+    return UFM_OK;
+}
+int ufm_batch_patch_layer(ufm_batch_t *b, int i, int k, const uint8_t *host_patch, int x, int y, int w, int h) { UFM_BATCH_MAP(b, i); return engine_patch_layer(e, li, k, host_patch, false, x, y, w, h); }
+int ufm_batch_patch_layer_device(ufm_batch_t *b, int i, int k, const uint8_t *dev_patch, int x, int y, int w, int h) { UFM_BATCH_MAP(b, i); return engine_patch_layer(e, li, k, dev_patch, true, x, y, w, h); }
+int ufm_batch_set_layer(ufm_batch_t *b, int i, int k, const uint8_t *host_raster, int width, int length) { UFM_BATCH_MAP(b, i); return engine_set_layer(e, li, k, host_raster, false, width, length); }
+int ufm_batch_set_layer_device(ufm_batch_t *b, int i, int k, const uint8_t *dev_raster, int width, int length) { UFM_BATCH_MAP(b, i); return engine_set_layer(e, li, k, dev_raster, true, width, length); }
+int ufm_batch_set_layer_survey(ufm_batch_t *b, int i, int k, const uint8_t *host_survey, int width, int length) { UFM_BATCH_MAP(b, i); return engine_set_layer_survey(e, li, k, host_survey, false, width, length); }
+int ufm_batch_set_layer_survey_device(ufm_batch_t *b, int i, int k, const uint8_t *dev_survey, int width, int length) { UFM_BATCH_MAP(b, i); return engine_set_layer_survey(e, li, k, dev_survey, true, width, length); }
+int ufm_batch_read_layer(ufm_batch_t *b, int i, int k, uint8_t *host_raster) { UFM_BATCH_MAP(b, i); return engine_read_layer(e, li, k, host_raster); }
+int ufm_batch_read_layer_survey(ufm_batch_t *b, int i, int k, uint8_t *host_survey) { UFM_BATCH_MAP(b, i); return engine_read_layer_survey(e, li, k, host_survey); }
 // The maps grouped by the device that owns them (contiguous blocks: a shard's centres are a slice of the caller's array): every shard is
 // checked before any of them launches; then one k_reveal per shard, queued side by side, and only then the counts are waited for.
 int ufm_batch_reveal(ufm_batch_t *b, const int32_t *centres, uint64_t *changed) {

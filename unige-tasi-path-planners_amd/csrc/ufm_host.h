@@ -303,6 +303,31 @@ struct Engine {
     size_t d_image_cap = 0;
     hipEvent_t prep_ev[2] = {nullptr, nullptr};   // profiling: on the k_prepare dispatch itself
     float prep_ms = 0.0f;            // ... its duration (tools/prepare_probe.py)
+    // Cost layers (ufm_set_layers / ufm_patch_layer / ufm_set_layer; ufm_layers.h).  n_layers == 1 -- the default --
+    // nothing below exists or runs.  With more, d_layers holds n rasters per map and the caller's raster (d_raw with a footprint, P.cost
+    // without) is their element-wise maximum between any two calls: a layer patch is stored, composed over its rectangle into the dense
+    // d_lcomp and that one goes to patch_raw() / patch() as the caller's device patch would -- never held for the block kernel, never
+    // deferred, both of which would put one layer's bytes into the composed raster.  Layer 0's survey is d_survey; layers 1 .. n-1 have
+    // d_lsurvey[k], and a reveal uncovers every layer that has one in ONE launch (k_reveal_layers).
+    int n_layers = 1;
+    uint8_t *d_layers = nullptr;     // [n_layers][nmaps] rasters at lstride bytes; dropped with the rasters (release())
+    size_t lstride = 0;
+    uint8_t *d_lsurvey[LAYERS_MAX] = {nullptr, nullptr, nullptr, nullptr};   // [nmaps][L][W] each ([0] stays null: d_survey); dropped with the rasters
+    std::vector<uint8_t> have_lsurvey[LAYERS_MAX];   // [nmaps] each
+    uint8_t *d_lcomp = nullptr;      // the dense composed patch of the layer call being applied
+    size_t d_lcomp_cap = 0;
+    int32_t *h_lcentres = nullptr;   // [nmaps][3], pinned + mapped: k_reveal_layers reads centres and survey bits from here
+    hipEvent_t lay_ev[2] = {nullptr, nullptr};   // profiling: on the dispatch of the last layer kernel
+    bool lay_timed = false;
+    uint8_t *layer_ptr(int k, int m) const { return d_layers + layers_slot(k, m, nmaps, lstride); }
+    int layer_surveys(int m) const {             // bit k: layer k of map m has a survey
+        int have = (d_survey && (size_t)m < have_survey.size() && have_survey[m]) ? 1 : 0;
+        for (int k = 1; k < n_layers; ++k) if (d_lsurvey[k] && (size_t)m < have_lsurvey[k].size() && have_lsurvey[k][m]) have |= 1 << k;
+        return have;
+    }
+    int layer_events(hipEvent_t *e0, hipEvent_t *e1);
+    int patch_layer(int m, int k, const uint8_t *dev_patch, int x, int y, int w, int h);
+    int reveal_layers(const int32_t *centres);
     // step deltas (ufm_track_changes / ufm_read_changes, ufm_delta.h): nothing below exists unless a caller turned tracking on
     bool track = false;
     float *trk_g = nullptr;          // the baseline: the field as the caller was last told, in the layout of P.G (same gstride)
@@ -333,6 +358,13 @@ void Engine::release() {
     if (d_survey) hipFree(d_survey);     // (a survey belongs to rasters of these dimensions)
     d_survey = nullptr;
     std::fill(have_survey.begin(), have_survey.end(), (uint8_t)0);
+    if (d_layers) hipFree(d_layers);     // (the layers and their surveys: rasters of these dimensions too)
+    d_layers = nullptr;
+    for (int k = 0; k < LAYERS_MAX; ++k) {
+        if (d_lsurvey[k]) hipFree(d_lsurvey[k]);
+        d_lsurvey[k] = nullptr;
+        std::fill(have_lsurvey[k].begin(), have_lsurvey[k].end(), (uint8_t)0);
+    }
     P = DevParams{};                     // every pointer null again: a failed alloc() can be released, and released twice
     d_scratch = nullptr;
     allocated = false;
@@ -403,6 +435,7 @@ int Engine::alloc(int width, int length) {
     dmalloc(P.ctr, sizeof(DevCounters));
     dmalloc(d_scratch, sizeof(int) * (4 * nmaps + 16));
     if (cs.on) dmalloc(d_raw, P.cstride * nmaps);
+    if (n_layers > 1) { lstride = layers_stride(P.cstride); dmalloc(d_layers, lstride * nmaps * n_layers); }
     if (rc != UFM_OK) { release(); return rc; }
     rc = [&]() -> int {
         // (the lists: a slot that was never written must still read as a tile id -- an in-launch reader may look at a slot its writer has claimed
@@ -425,6 +458,7 @@ int Engine::alloc(int width, int length) {
         HIPCHK(hipMemsetAsync(P.mark, 0, P.mstride * nmaps, stream));
         HIPCHK(hipMemsetAsync(P.num_updated, 0, sizeof(unsigned int) * nmaps, stream));
         HIPCHK(hipMemsetAsync(P.goal, 0xFF, sizeof(int) * 2 * nmaps, stream));
+        if (d_layers) HIPCHK(hipMemsetAsync(d_layers, 0, lstride * nmaps * n_layers, stream));
         k_fill<<<1024, 256, 0, stream>>>(P.G, P.gstride * nmaps, INFINITY);
         k_fill<<<1024, 256, 0, stream>>>(P.Gprev, P.gstride * nmaps, INFINITY);
         HIPCHK(hipMemsetAsync(P.bp, BP_NONE, P.gstride * nmaps, stream));
@@ -736,6 +770,7 @@ int Engine::patch_lazy(int m, const uint8_t *host_patch, int x, int y, int w, in
     if (x < 0 || y < 0 || w <= 0 || h <= 0 || x + h > L || y + w > W) return UFM_ERR_INVALID;   // Graph.cpp:38-41
     if (cs.on) return UFM_OK;          // (a footprint: the block kernel would apply raw bytes to the planning raster)
     if (census_on) return UFM_OK;      // (the census: the block kernel would change the raster behind the counters' back)
+    if (n_layers > 1) return UFM_OK;   // (layers: the block kernel would put one layer's bytes into the composed raster)
     if (!(lazy_patches && nmaps == 1 && use_region && fuse_control && spin_wait && w <= 64 && h <= 64)) return UFM_OK;
     if ((int)lazy.size() >= LAZY_SLOTS || pending.size() != lazy.size()) return UFM_OK;      // (only behind other held patches: the block kernel applies them in order)
     if (!h_lazy) HIPCHK(hipHostMalloc(&h_lazy, (size_t)LAZY_SLOTS * 4096, hipHostMallocMapped));
@@ -759,7 +794,7 @@ int Engine::patch(int m, const uint8_t *dev_patch, int x, int y, int w, int h, b
     { int rc = ensure_pmask((size_t)n); if (rc != UFM_OK) return rc; }
     // (a batch only: the patch kernel of a single map runs while the host prepares the step -- applying it inside the
     //  replan's block kernel instead was tried and saved nothing, it only made that kernel longer)
-    if (may_defer && defer_patches && !census_on && nmaps > 1 && n <= 4096) {
+    if (may_defer && defer_patches && !census_on && n_layers == 1 && nmaps > 1 && n <= 4096) {
         // (one per map at a time: two patches of one map may overlap, and then their order counts)
         bool clash = (int)deferred.size() >= PATCH_MULTI;
         for (const DeferredPatch &d : deferred) clash = clash || d.m == m;
@@ -840,6 +875,14 @@ void Engine::census_free() {
 // ---- the sensor reveal: a move uncovers the survey raster's field of view, as a patch made on the device ----
 // everything a reveal of these centres ([nmaps][2], row < 0: skipped) needs; nothing is launched or written
 int Engine::reveal_check(const int32_t *centres) const {
+    if (n_layers > 1) {                  // (layers: any layer's survey will do, every map that is not skipped needs one)
+        if (!centres || !sensor.set || !allocated) return UFM_ERR_INVALID;
+        for (int m = 0; m < nmaps; ++m) {
+            if (centres[2 * m] < 0) continue;
+            if (!maps[m].have_map || !layer_surveys(m) || !sensor_centre_ok(centres[2 * m], centres[2 * m + 1], L, W)) return UFM_ERR_INVALID;
+        }
+        return UFM_OK;
+    }
     if (!centres || !sensor.set || !allocated || !d_survey) return UFM_ERR_INVALID;
     for (int m = 0; m < nmaps; ++m) {
         if (centres[2 * m] < 0) continue;
@@ -850,6 +893,7 @@ int Engine::reveal_check(const int32_t *centres) const {
 // One k_reveal for all maps, then every map's slot through the route its device patch would take.  As in patch_raw(), whatever can fail
 // -- applying what is held, the growth of the buffers -- comes before the first write to a raster.
 int Engine::reveal(const int32_t *centres) {
+    if (n_layers > 1) return reveal_layers(centres);
     { int rc = reveal_check(centres); if (rc != UFM_OK) return rc; }
     bool any = false;
     for (int m = 0; m < nmaps; ++m) any = any || centres[2 * m] >= 0;
@@ -896,6 +940,110 @@ int Engine::reveal_counts(const int32_t *centres, uint64_t *changed) {
     HIPCHK(hipStreamSynchronize(stream));
     reveal_busy = false;
     for (int m = 0; m < nmaps; ++m) changed[m] = centres[2 * m] >= 0 ? cnt[m] : 0u;
+    return UFM_OK;
+}
+
+// ---- cost layers: the caller's raster == max over the layers, kept at a cost proportional to the patch ----
+// profiling: the events the next layer kernel's dispatch carries (null while profiling is off)
+int Engine::layer_events(hipEvent_t *e0, hipEvent_t *e1) {
+    *e0 = *e1 = nullptr;
+    lay_timed = false;
+    if (!profiling) return UFM_OK;
+    for (auto &e : lay_ev) if (!e) HIPCHK(hipEventCreate(&e));
+    *e0 = lay_ev[0]; *e1 = lay_ev[1];
+    lay_timed = true;
+    return UFM_OK;
+}
+// The buffers a composed patch of n cells needs on its way through patch_raw() / patch(): as there, whatever can fail -- applying what is
+// held, the growth of the buffers -- comes before the first write to any store.
+static int layers_make_room(Engine *e, int m, int x, int y, int w, int h) {
+    { int rc = e->flush_deferred(); if (rc != UFM_OK) return rc; }
+    size_t largest = (size_t)w * h;
+    if (e->cs.on) {
+        const PatchRect g = grow_rect(PatchRect{m, x, y, w, h}, e->cs.mh, e->cs.mw, e->cs.ar, e->cs.ac, e->L, e->W);
+        largest = (size_t)g.w * g.h;
+        if (largest > e->d_cs_patch_cap) {
+            const size_t cap = std::max<size_t>(largest, 4096);
+            { int rc = regrow(e->stream, cap, e->d_cs_patch_cap, cap, e->d_cs_patch); if (rc != UFM_OK) return rc; }
+        }
+    }
+    return e->ensure_pmask(largest);
+}
+// ufm_patch_layer*, stream-ordered: the bytes into layer k, the maximum over the layers of that rectangle into the dense scratch patch,
+// that one through the route the caller's device patch takes.  The whole map (ufm_set_layer): a copy and the vector kernel.
+int Engine::patch_layer(int m, int k, const uint8_t *dev_patch, int x, int y, int w, int h) {
+    if (m < 0 || m >= nmaps || !allocated || !maps[m].have_map || !layers_index_ok(k, n_layers)) return UFM_ERR_INVALID;
+    if (!layers_rect_ok(x, y, w, h, L, W)) return UFM_ERR_INVALID;            // Graph.cpp:38-41
+    const size_t n = (size_t)w * h;
+    if (n > d_lcomp_cap) {
+        const size_t cap = std::max<size_t>(n, 4096);
+        { int rc = regrow(stream, cap, d_lcomp_cap, cap, d_lcomp); if (rc != UFM_OK) return rc; }
+    }
+    { int rc = layers_make_room(this, m, x, y, w, h); if (rc != UFM_OK) return rc; }
+    hipEvent_t e0, e1;
+    { int rc = layer_events(&e0, &e1); if (rc != UFM_OK) return rc; }
+    if (layers_rect_is_map(x, y, w, h, L, W)) {
+        HIPCHK(hipMemcpyAsync(layer_ptr(k, m), dev_patch, n, hipMemcpyDeviceToDevice, stream));
+        LayerComposeAllJob j{};
+        for (int l = 0; l < n_layers; ++l) j.layer[l] = layer_ptr(l, m);
+        j.out = d_lcomp; j.cells = n; j.n = n_layers;
+        const LayersSplit s = layers_split(reinterpret_cast<uintptr_t>(j.out), n);
+        launch(k_layer_compose_all, dim3(layers_all_grid(s.nvec)), dim3(LAYERS_THREADS), stream, e0, e1, j);
+    } else {
+        LayerComposeJob j{};
+        for (int l = 0; l < n_layers; ++l) j.layer[l] = layer_ptr(l, m);
+        j.patch = dev_patch; j.out = d_lcomp;
+        j.n = n_layers; j.k = k; j.W = W; j.x = x; j.y = y; j.w = w; j.h = h;
+        launch(k_layer_compose, dim3(layers_rect_grid(w * h)), dim3(LAYERS_THREADS), stream, e0, e1, j);
+    }
+    HIPCHK(hipGetLastError());
+    return cs.on ? patch_raw(m, d_lcomp, x, y, w, h) : patch(m, d_lcomp, x, y, w, h, false);
+}
+// ufm_reveal* with n > 1: one k_reveal_layers for all layers of all maps, then every map's slot through the route its device patch takes
+// (patch() declines the deferral while there are layers)
+int Engine::reveal_layers(const int32_t *centres) {
+    { int rc = reveal_check(centres); if (rc != UFM_OK) return rc; }
+    bool any = false;
+    for (int m = 0; m < nmaps; ++m) any = any || centres[2 * m] >= 0;
+    if (!any) return UFM_OK;
+    { int rc = flush_deferred(); if (rc != UFM_OK) return rc; }
+    const size_t stride = sensor_slot_stride(sensor.mw, sensor.mh), need = stride * (size_t)nmaps;
+    if (need > d_reveal_cap) { int rc = regrow(stream, need, d_reveal_cap, need, d_reveal); if (rc != UFM_OK) return rc; }
+    size_t largest = (size_t)sensor.mw * sensor.mh;
+    if (cs.on) {
+        largest = (size_t)(sensor.mw + cs.mw - 1) * (size_t)(sensor.mh + cs.mh - 1);
+        if (largest > d_cs_patch_cap) {
+            const size_t cap = std::max<size_t>(largest, 4096);
+            { int rc = regrow(stream, cap, d_cs_patch_cap, cap, d_cs_patch); if (rc != UFM_OK) return rc; }
+        }
+    }
+    { int rc = ensure_pmask(largest); if (rc != UFM_OK) return rc; }
+    if (!h_lcentres) HIPCHK(hipHostMalloc(&h_lcentres, sizeof(int32_t) * 3 * (size_t)nmaps, hipHostMallocMapped));
+    if (reveal_busy) { HIPCHK(hipStreamSynchronize(stream)); reveal_busy = false; }
+    for (int m = 0; m < nmaps; ++m) {
+        h_lcentres[3 * m] = centres[2 * m]; h_lcentres[3 * m + 1] = centres[2 * m + 1];
+        h_lcentres[3 * m + 2] = layer_surveys(m);
+    }
+    __atomic_thread_fence(__ATOMIC_RELEASE);
+    HIPCHK(hipMemsetAsync(d_reveal_cnt, 0, sizeof(unsigned int) * nmaps, stream));
+    RevealLayersJob j{};
+    j.mask = d_sensor; j.layers = d_layers; j.cur = cs.on ? d_raw : P.cost; j.slots = d_reveal; j.count = d_reveal_cnt; j.centres = h_lcentres;
+    j.survey[0] = d_survey;
+    for (int k = 1; k < n_layers; ++k) j.survey[k] = d_lsurvey[k];
+    j.cstride = P.cstride; j.lstride = lstride; j.slot_stride = stride;
+    j.n = n_layers; j.nmaps = nmaps; j.L = L; j.W = W; j.mh = sensor.mh; j.mw = sensor.mw; j.ar = sensor.ar; j.ac = sensor.ac;
+    hipEvent_t e0, e1;
+    { int rc = layer_events(&e0, &e1); if (rc != UFM_OK) return rc; }
+    launch(k_reveal_layers, dim3(sensor_grid_x(sensor.mw, sensor.mh), nmaps), dim3(SENSOR_THREADS), stream, e0, e1, j);
+    HIPCHK(hipGetLastError());
+    reveal_busy = true;
+    for (int m = 0; m < nmaps; ++m) {
+        if (centres[2 * m] < 0) continue;
+        const SensorRect r = sensor_place(centres[2 * m], centres[2 * m + 1], sensor.mh, sensor.mw, sensor.ar, sensor.ac, L, W);
+        const uint8_t *slot = d_reveal + stride * (size_t)m;
+        const int rc = cs.on ? patch_raw(m, slot, r.x, r.y, r.w, r.h) : patch(m, slot, r.x, r.y, r.w, r.h, true);
+        if (rc != UFM_OK) return rc;
+    }
     return UFM_OK;
 }
 
@@ -1429,6 +1577,9 @@ int engine_destroy(Engine *e) {
     e->census_free();
     free_all(hipFree, e->d_sensor, e->d_reveal, e->d_reveal_cnt, e->d_image);
     free_all(hipHostFree, e->h_centres);
+    for (hipEvent_t v : e->lay_ev) if (v) hipEventDestroy(v);
+    free_all(hipFree, e->d_lcomp);
+    free_all(hipHostFree, e->h_lcentres);
     free_all(hipFree, e->d_cs_patch, e->d_patch, e->d_pmask, e->d_field, e->d_info, e->d_jobs, e->d_path);
     free_all(hipHostFree, e->h_jobs, e->h_path, e->h_patch, e->h_lazy);
     e->drop_graphs();
@@ -1455,6 +1606,10 @@ template <class Fill> int engine_new_raster(Engine *e, int m, int width, int len
     }
     // (a footprint: the input is the raw raster -- kept, and dilated into the planning raster before anything reads that one)
     { int rc = fill((e->cs.on ? e->d_raw : e->P.cost) + (size_t)m * e->P.cstride); if (rc != UFM_OK) return rc; }
+    if (e->n_layers > 1) {   // (layers: the argument is layer 0, the others start at zero -- rock_aboundance_l = np.zeros(...), run_test.py:102)
+        HIPCHK(hipMemcpyAsync(e->layer_ptr(0, m), (e->cs.on ? e->d_raw : e->P.cost) + (size_t)m * e->P.cstride, e->P.cstride, hipMemcpyDeviceToDevice, e->stream));
+        for (int k = 1; k < e->n_layers; ++k) HIPCHK(hipMemsetAsync(e->layer_ptr(k, m), 0, e->P.cstride, e->stream));
+    }
     if (e->cs.on) e->cspace_dilate(m, e->P.cost + (size_t)m * e->P.cstride, width, PatchRect{m, 0, 0, width, length});
     if (e->census_on) { e->census_build(m); e->census_publish(); }      // (the planning raster is final; published by the wait below)
     k_cost_windows<<<2048, 256, 0, e->stream>>>(e->P, m);
@@ -1524,8 +1679,48 @@ int engine_set_image(Engine *e, int m, const uint8_t *src, bool on_device, int w
     return UFM_OK;
 }
 
+// ufm_patch_layer* / ufm_batch_patch_layer*, and ufm_patch_map* while there are layers (k = 0): checked whole before the staging copy
+int engine_patch_layer(Engine *e, int m, int k, const uint8_t *src, bool on_device, int x, int y, int w, int h) {
+    if (!e || !src || m < 0 || m >= e->nmaps || !e->allocated || !e->maps[m].have_map) return UFM_ERR_INVALID;
+    if (!layers_index_ok(k, e->n_layers) || !layers_rect_ok(x, y, w, h, e->L, e->W)) return UFM_ERR_INVALID;
+    HIPCHK(hipSetDevice(e->device));
+    if (on_device) return e->patch_layer(m, k, src, x, y, w, h);
+    const size_t n = (size_t)w * h;
+    if (n > e->d_patch_cap) {
+        const size_t cap = n < 4096 ? 4096 : n;
+        { int rc = regrow(e->stream, cap, e->d_patch_cap, cap, e->d_patch, &e->h_patch); if (rc != UFM_OK) return rc; }
+    } else {
+        HIPCHK(hipStreamSynchronize(e->stream));   // staging buffers are reused
+    }
+    std::memcpy(e->h_patch, src, n);
+    HIPCHK(hipMemcpyAsync(e->d_patch, e->h_patch, n, hipMemcpyHostToDevice, e->stream));
+    return e->patch_layer(m, k, e->d_patch, x, y, w, h);
+}
+// ufm_set_layer*: layer k wholesale, a whole-map patch -- not a set_map: the field is kept and the next step replans
+int engine_set_layer(Engine *e, int m, int k, const uint8_t *src, bool on_device, int width, int length) {
+    if (!e || !e->allocated || width != e->W || length != e->L) return UFM_ERR_INVALID;
+    return engine_patch_layer(e, m, k, src, on_device, 0, 0, width, length);
+}
+// ufm_set_layers / ufm_batch_set_layers: a property of the handle, set before the first raster
+int engine_set_layers(Engine *e, int n) {
+    if (!e || !layers_count_ok(n)) return UFM_ERR_INVALID;
+    for (const MapState &ms : e->maps) if (ms.have_map) return UFM_ERR_INVALID;
+    // (arrays without a map -- a ufm_set_map that failed after its allocation -- were sized for the old count: the next one allocates anew)
+    if (e->allocated) { HIPCHK(hipSetDevice(e->device)); e->release(); }
+    e->n_layers = n;
+    return UFM_OK;
+}
+int engine_read_layer(Engine *e, int m, int k, uint8_t *out) {
+    if (!e || !out || m < 0 || m >= e->nmaps || !e->allocated || !e->maps[m].have_map || !layers_index_ok(k, e->n_layers)) return UFM_ERR_INVALID;
+    HIPCHK(hipSetDevice(e->device));
+    HIPCHK(hipMemcpyAsync(out, e->layer_ptr(k, m), e->P.cstride, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return UFM_OK;
+}
+
 int engine_patch(Engine *e, int m, const uint8_t *src, bool on_device, int x, int y, int w, int h) {
     if (!e || !src) return UFM_ERR_INVALID;
+    if (e->n_layers > 1) return engine_patch_layer(e, m, 0, src, on_device, x, y, w, h);
     HIPCHK(hipSetDevice(e->device));
     if (on_device) return e->cs.on ? e->patch_raw(m, src, x, y, w, h) : e->patch(m, src, x, y, w, h, true);
     if (w <= 0 || h <= 0) return UFM_ERR_INVALID;
@@ -1608,6 +1803,31 @@ int engine_read_survey(Engine *e, int m, uint8_t *host_survey) {
     if (!e || !host_survey || m < 0 || m >= e->nmaps || !e->allocated || !e->d_survey || !e->have_survey[m]) return UFM_ERR_INVALID;
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipMemcpyAsync(host_survey, e->d_survey + (size_t)m * e->P.cstride, e->P.cstride, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));
+    return UFM_OK;
+}
+
+// ufm_set_layer_survey* / ufm_batch_set_layer_survey*: what the sensor would see of layer k of map m; k = 0 is ufm_set_survey
+int engine_set_layer_survey(Engine *e, int m, int k, const uint8_t *src, bool on_device, int width, int length) {
+    if (k == 0) return engine_set_survey(e, m, src, on_device, width, length);
+    if (!e || !src || m < 0 || m >= e->nmaps || !e->allocated || !e->maps[m].have_map || width != e->W || length != e->L) return UFM_ERR_INVALID;
+    if (!layers_index_ok(k, e->n_layers)) return UFM_ERR_INVALID;
+    HIPCHK(hipSetDevice(e->device));
+    if (!e->d_lsurvey[k]) {
+        if (hipMalloc(&e->d_lsurvey[k], e->P.cstride * e->nmaps) != hipSuccess) { (void)hipGetLastError(); e->d_lsurvey[k] = nullptr; return UFM_ERR_NOMEM; }
+        e->have_lsurvey[k].assign((size_t)e->nmaps, 0);
+    }
+    HIPCHK(hipMemcpyAsync(e->d_lsurvey[k] + (size_t)m * e->P.cstride, src, e->P.cstride, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipStreamSynchronize(e->stream));      // (the caller's buffer is free again when the call returns)
+    e->reveal_busy = false;
+    e->have_lsurvey[k][m] = 1;
+    return UFM_OK;
+}
+int engine_read_layer_survey(Engine *e, int m, int k, uint8_t *host_survey) {
+    if (!e || !host_survey || m < 0 || m >= e->nmaps || !e->allocated || !layers_index_ok(k, e->n_layers) || !((e->layer_surveys(m) >> k) & 1)) return UFM_ERR_INVALID;
+    HIPCHK(hipSetDevice(e->device));
+    const uint8_t *src = (k == 0 ? e->d_survey : e->d_lsurvey[k]) + (size_t)m * e->P.cstride;
+    HIPCHK(hipMemcpyAsync(host_survey, src, e->P.cstride, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     return UFM_OK;
 }

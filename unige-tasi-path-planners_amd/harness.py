@@ -167,7 +167,7 @@ class Pipes:
 def run_mission(cmd, pipe_to_planner, pipe_from_planner, img_h, start, goal, radius=5, cspace_diameter=1,
                 low_res_penalty=10, use_heuristic=False, max_moves=10000, on_map=None, on_move=None, display_shift=0.0,
                 append_pipes=True, tof=False, on_expanded=None, planner_inflates=False, planner_min_cost=False, planner_senses=False,
-                planner_prepares=False, filter_size=3):
+                planner_prepares=False, filter_size=3, layers=None, planner_layers=False):
     """One mission as Tests/run_test.py:85-177 runs it: launch the planner process `cmd`, send the
     C-space of the low-resolution map, then per robot position reveal the disc of radius `radius`,
     send its bounding patch and the heuristic hint, receive the planned path.  start / goal are
@@ -189,7 +189,18 @@ def run_mission(cmd, pipe_to_planner, pipe_from_planner, img_h, start, goal, rad
     P = low_res_penalty): where the map raster would go, the grey-scale bitmap img_h goes out, framed the same way, and with
     planner_senses no survey message follows it -- the planner has made that too.  The low-resolution map is then the planner's to
     inflate: a cspace_diameter above 1 needs planner_inflates.  on_map still gets the map the reference would have sent.
+    layers: further high-resolution cost rasters of the bitmap's shape, in addition to the bitmap-derived one (Tests/run_test.py:102: slope
+    and rocks).  Each has a known low-resolution counterpart that starts at zero; every move uncovers the same disc in all of them
+    (round_patch_update per layer) and the map is their np.maximum, dilated (run_test.py:136-140).  Without planner_layers all of that
+    happens here and the COMPOSED patches are shipped, as the reference does.
+    planner_layers: the planner process keeps the layers itself (ufm_planner --layers N with N = 1 + len(layers); needs planner_senses):
+    the extra high-resolution rasters go out ONCE, behind the survey (or behind the bitmap with planner_prepares), positions thereafter.
     Returns the list of positions visited and whether the planner reported the end."""
+    layers = [np.ascontiguousarray(a, dtype=np.uint8) for a in (layers or [])]
+    if planner_layers and not planner_senses:
+        raise ValueError("planner_layers: the planner uncovers the layers itself, so it must sense too (planner_senses)")
+    if any(a.shape != np.shape(img_h) for a in layers):
+        raise ValueError("layers: every raster has the bitmap's shape")
     if planner_prepares and cspace_diameter > 1 and not planner_inflates:
         raise ValueError("planner_prepares: the planner makes the raw map, so it must inflate it too (planner_inflates)")
     for p in (pipe_to_planner, pipe_from_planner):
@@ -216,6 +227,10 @@ def run_mission(cmd, pipe_to_planner, pipe_from_planner, img_h, start, goal, rad
             io.send_bytes(np.ascontiguousarray(data_l if planner_inflates else cspace).tobytes())
         if planner_senses and not planner_prepares:
             io.send_bytes(np.ascontiguousarray(data_h).tobytes())
+        if planner_layers:
+            for a in layers:
+                io.send_bytes(a.tobytes())
+        known = [np.zeros_like(a) for a in layers]       # rock_aboundance_l = np.zeros(...), run_test.py:102: the map starts as data_l alone
         if start is not None:
             io.send("ffffB", float(start[0]), float(start[1]), float(goal[0]), float(goal[1]), 1 if tof else 0)
         io.send("i", min_cost)
@@ -237,10 +252,12 @@ def run_mission(cmd, pipe_to_planner, pipe_from_planner, img_h, start, goal, rad
             trace.append((x, y))
             center = (int(round(yr)), int(round(xr)))         # (col, row) of the position as received, run_test.py:143
             data_l, (top, left), ranges = round_patch_update(data_l, data_h, center, radius)
-            cspace = dilate(data_l, cspace_diameter) if host_inflates else data_l
-            patch = np.ascontiguousarray((data_l if planner_inflates else cspace)[ranges[0], ranges[1]])
+            known = [round_patch_update(k, a, center, radius)[0] for k, a in zip(known, layers)]      # run_test.py:136-139: the same disc in every layer
+            raw = np.maximum.reduce([data_l] + known)                                                # :140
+            cspace = dilate(raw, cspace_diameter) if host_inflates else raw
+            patch = np.ascontiguousarray((raw if planner_inflates else cspace)[ranges[0], ranges[1]])
             if use_heuristic:
-                min_cost = int(data_l.min()) if planner_min_cost else int(cspace.min())
+                min_cost = int(raw.min()) if planner_min_cost else int(cspace.min())
             io.send("b", 1)
             if planner_senses:
                 io.send("iiii", top, left, 0, 0)

@@ -84,6 +84,17 @@ class ReplannerBase {
     if (rc != UFM_OK) last_error = rc;
     return rc;
   }
+  /** Cost layers on the device (ufm_set_layers / ufm_patch_layer / ufm_set_layer / ufm_set_layer_survey; no reference counterpart: the
+   *  reference's simulator keeps slope and rocks on the host and ships np.maximum of them, Tests/run_test.py:102,136-140): n rasters per
+   *  map whose element-wise maximum is the raster the planner sees, set before the first set_map -- which feeds layer 0, as patch_map
+   *  does.  patch_layer / set_layer store into layer k and patch the map with the maximum; with a survey per layer reveal() uncovers
+   *  every layer at once.  `grid` keeps what set_map / patch_map were handed: it follows neither the other layers nor reveals. */
+  int set_layers(int n) { return noted(ufm_set_layers(handle_, n)); }
+  int patch_layer(int k, const std::shared_ptr<uint8_t> &patch, int x, int y, int w, int h) { return noted(ufm_patch_layer(handle_, k, patch.get(), x, y, w, h)); }
+  int set_layer(int k, const std::shared_ptr<uint8_t> &raster, int w, int h) { return noted(ufm_set_layer(handle_, k, raster.get(), w, h)); }
+  int set_layer_survey(int k, const std::shared_ptr<uint8_t> &survey, int w, int h) { return noted(ufm_set_layer_survey(handle_, k, survey.get(), w, h)); }
+  int read_layer(int k, uint8_t *out) { return noted(ufm_read_layer(handle_, k, out)); }
+  int read_layer_survey(int k, uint8_t *out) { return noted(ufm_read_layer_survey(handle_, k, out)); }
   /** Cost census (ufm_track_costs; no reference counterpart: the reference's simulator takes cv2.minMaxLoc of the map it inflated itself,
    *  run_simulator.py:152,183): exact counts of the PLANNING raster's values, kept under patches.  min_cost(): the smallest value present,
    *  -1 if the census is off or no map is set; cost_census(): all 256 counters, returns the ufm code. */
@@ -187,6 +198,7 @@ class ReplannerBase {
 
  private:
   void check(int rc) { if (rc != UFM_OK) last_error = rc; }
+  int noted(int rc) { check(rc); return rc; }
   ufm_t *handle_ = nullptr;
   bool auto_heuristic_ = false;
   float used_multiplier_ = 1;
