@@ -1186,8 +1186,15 @@ int Engine::submit_block(StepRun &r) {
     else { dyn_dev = r.dyn_now; r.dyn_pending = false; }
     const bool reg_timed = profiling && (region_runs & 7u) == 0u;     // a sample: the event packets cost a few microseconds each
     if (reg_timed) for (auto &e : reg_ev) if (!e) HIPCHK(hipEventCreate(&e));
+    // the kernel's form (ufm_region.h, RF_*): the diagnostics bring everything with them; otherwise the heuristic term only where the keys have one
+    const int form = region_debug ? (RF_HEUR | RF_DEBUG) : (r.dyn_now.hm != 0.0f ? RF_HEUR : 0);
     with_raise_op(algo, dfm_follow_info, [&](auto a) {
-        launch(k_replan_region<a()>, dim3(rjs.n), dim3(NTHR), stream, reg_timed ? reg_ev[0] : nullptr, reg_timed ? reg_ev[1] : nullptr, P, rjs, h_ctr, h_flag);
+        auto go = [&](auto f) {
+            launch(k_replan_region<a(), f()>, dim3(rjs.n), dim3(NTHR), stream, reg_timed ? reg_ev[0] : nullptr, reg_timed ? reg_ev[1] : nullptr, P, rjs, h_ctr, h_flag);
+        };
+        if (form == 0) go(IntC<0>{});
+        else if (form == RF_HEUR) go(IntC<RF_HEUR>{});
+        else go(IntC<(RF_HEUR | RF_DEBUG)>{});
     });
     HIPCHK(hipGetLastError());
     last_active = 1;

@@ -55,6 +55,11 @@ struct RegionJob {
 // map, all in one launch.
 constexpr int RJOBS = 8;
 struct RegionJobs { int n; RegionJob j[RJOBS]; };
+// The forms of the kernel (Engine::submit_block chooses per launch).  The common job -- no heuristic term in the keys, no diagnostics -- runs a
+// form that carries neither: no heuristic distance per burst, no diagnostics switches, counters or time stamps (state the kernel, which spills
+// scalar registers into vector lanes on its burst path, otherwise keeps for nothing).  Three are instantiated: 0 (lean), RF_HEUR,
+// RF_HEUR | RF_DEBUG (everything; RegionJob::debug is only looked at there).
+constexpr int RF_HEUR = 1, RF_DEBUG = 2;
 
 // a priority this very kernel may have written (agent-scope load: past the CU's L1)
 __device__ __forceinline__ int prio_read_fresh(const DevParams &P, int qz, int kk, int gt) {
@@ -90,6 +95,10 @@ struct RegionShared {
     int expanded;
     int m_r, m_l, done;
     int dkey;                             // smallest KEY (value + hm * dist) lowering held back in the current sub-round (float bits)
+    int pkey[16][RWW * 32];               // per patch: the smallest key its LAST lowering burst held back (float bits; INFBITS: nothing).  S.dkey is their
+                                          // minimum at the end of a sub-round, when every patch has been swept on the values as they stand -- not the minimum
+                                          // over all bursts of the sub-round: a burst that ran before its neighbours were lowered holds back a result the
+                                          // patch's later bursts apply, and with such a key in it the next band depended on how the waves had interleaved
     int dbg[8];                           // diagnostics
     int dbg2[8];                          // diagnostics: [0] lowering bursts that changed nothing, [1] ... whose patch and its 1-element surround held nothing but +inf, [2] invalidation bursts that changed nothing
     unsigned long long tstamp[12];        // diagnostics: wall_clock64 at the phase boundaries
@@ -132,11 +141,12 @@ __device__ __forceinline__ float region_lower_bound(const float *Gs, const Regio
 }
 
 // One phase (MODE_RAISE: invalidation, MODE_LOWER: lowering) of the block to quiescence.  All 16 waves call.
-// ALGOF: the operator id, with ALGO_FOLLOW_INFO for MS-DFM level 1's invalidation along its stored bytes.
-template <int ALGOF, int MODE>
+// ALGOF: the operator id, with ALGO_FOLLOW_INFO for MS-DFM level 1's invalidation along its stored bytes.  FORM: the kernel's form (RF_*).
+template <int ALGOF, int MODE, int FORM>
 __device__ void region_phase(const DevParams &P, const RegionJob &J, float *Gs, const uint8_t *Cb, uint8_t *Bb, RegionShared &S,
                              int thr, float hm, int focused, int goal_lx, int goal_ly) {
     constexpr int ALGO = algo_of(ALGOF);
+    constexpr bool HEUR = (FORM & RF_HEUR) != 0, DBG = (FORM & RF_DEBUG) != 0;
     constexpr bool FOLLOW = (ALGOF & ALGO_FOLLOW_INFO) != 0;
     constexpr bool BPRAISE = MODE == MODE_RAISE && (!is_dfm<ALGO> || FOLLOW);   // invalidation along the stored back-pointers (k_relax)
     const int tid = threadIdx.x, w = wave_index16(tid >> 6), lane = tid & 63;
@@ -166,7 +176,7 @@ __device__ void region_phase(const DevParams &P, const RegionJob &J, float *Gs, 
     const int so2 = __builtin_amdgcn_readfirstlane(S.soff[2]), so3 = __builtin_amdgcn_readfirstlane(S.soff[3]);
     // (J lives in the kernel's argument segment: a field of it read inside the sweep loop is a scalar memory load, waited for, in
     //  every sweep -- J.debug was)
-    const bool dbg_nogate = (J.debug & 1) != 0, dbg_count = (J.debug & 2) != 0;
+    const bool dbg_nogate = DBG && (J.debug & 1) != 0, dbg_count = DBG && (J.debug & 2) != 0;
     const float Bphase = (MODE == MODE_LOWER) ? S.Bgate : INFINITY;
     const float rb_phase = S.rbound + J.slack;
     // words of this wave that can hold a bit at all (a block smaller than RTMAX x RTMAX leaves the upper ones empty)
@@ -228,7 +238,7 @@ __device__ void region_phase(const DevParams &P, const RegionJob &J, float *Gs, 
                 const int nwave = wt_wave, nword = wt_ok ? (ni >> 5) : -1, nbit = 1 << (ni & 31);
                 // admissible part of the key that does not depend on the value: hm * dist(start, patch)
                 float hd = 0.0f;
-                if (hm != 0.0f) {
+                if (HEUR && hm != 0.0f) {
                     const float x0 = (float)(rx0 + pr * 4), x1 = x0 + 3.0f, y0 = (float)(ry0 + pc * 4), y1 = y0 + 3.0f;
                     const float dx = fmaxf(fmaxf(x0 - sx, sx - x1), 0.0f), dy = fmaxf(fmaxf(y0 - sy, sy - y1), 0.0f);
                     hd = hm * hypotf(dx, dy) * 0.999f;
@@ -312,10 +322,11 @@ __device__ void region_phase(const DevParams &P, const RegionJob &J, float *Gs, 
                 if (MODE == MODE_RAISE && rmin_l < INFINITY && q == 0) { atomicMin(&S.rmin, __float_as_int(rmin_l)); S.traised[tl] = 1; }
                 if (dbg_count && lane == 0) { atomicAdd(&S.dbg[MODE == MODE_LOWER ? 5 : 4], 1); atomicAdd(&S.dbg[MODE == MODE_LOWER ? 7 : 6], cnt); if (!pch) atomicAdd(&S.dbg2[MODE == MODE_LOWER ? 0 : 2], 1); }
                 if (again && lane == 0) __hip_atomic_fetch_or(&S.wake[w][wd], 1 << j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   // burst cap
+                if (MODE == MODE_LOWER && lane == 0) __hip_atomic_store(&S.pkey[w][idx], INFBITS, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   // (this wave's own patch; its LDS accesses stay in order)
                 if (dmin < INFINITY && q == 0) {
-                    atomicAdd(&S.dbg[MODE == MODE_LOWER ? 0 : 1], 1);
+                    if (DBG) atomicAdd(&S.dbg[MODE == MODE_LOWER ? 0 : 1], 1);
                     atomicMin(&S.dprio[MODE == MODE_LOWER ? 0 : 1][tl], __float_as_int(dmin));      // the tile's priority when it is parked
-                    if (MODE == MODE_LOWER) atomicMin(&S.dkey, __float_as_int(dmin + hd));          // what the gate compared with the start's key
+                    if (MODE == MODE_LOWER) atomicMin(&S.pkey[w][idx], __float_as_int(dmin + hd));  // what the gate compared with the start's key
                     __hip_atomic_fetch_or(&S.defer[MODE == MODE_LOWER ? 0 : 1][w][wd], 1 << j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 }
             }
@@ -356,9 +367,10 @@ __device__ void region_phase(const DevParams &P, const RegionJob &J, float *Gs, 
     __syncthreads();
 }
 
-template <int ALGOF>   // (the operator id, with ALGO_FOLLOW_INFO: region_phase)
+template <int ALGOF, int FORM>   // (the operator id, with ALGO_FOLLOW_INFO, and the form: region_phase)
 __global__ __launch_bounds__(NTHR) void k_replan_region(DevParams P, RegionJobs JS, DevCounters *host, unsigned int *flag) {
     constexpr int ALGO = algo_of(ALGOF);
+    constexpr bool HEUR = (FORM & RF_HEUR) != 0, DBG = (FORM & RF_DEBUG) != 0;
     __shared__ float Gs[(RN + 2) * RP];
     __shared__ uint8_t Cb[(RN + 1) * RCP];
     __shared__ __attribute__((aligned(16))) uint8_t Bb[RN * RBP];
@@ -386,11 +398,12 @@ __global__ __launch_bounds__(NTHR) void k_replan_region(DevParams P, RegionJobs 
     const int nty_magic = (65536 + J.nty - 1) / J.nty;
     const int rx0 = J.tx0 * T, ry0 = J.ty0 * T, rnx = J.ntx * T, rny = J.nty * T;
 
-    const unsigned long long t_begin = wall_clock64();
-#define STAMP(k) do { if (tid == 0 && (J.debug & 2)) s_tb[k] = wall_clock64(); } while (0)
+    const int debug = DBG ? J.debug : 0;                      // (the diagnostics, their time stamps included, are the full form's alone)
+    const unsigned long long t_begin = DBG ? wall_clock64() : 0ull;
+#define STAMP(k) do { if (DBG && tid == 0 && (debug & 2)) s_tb[k] = wall_clock64(); } while (0)
     STAMP(0);
-    if ((tid & 63) == 0 && (J.debug & 2)) s_simd[tid >> 6] = (int)__builtin_amdgcn_s_getreg((1 << 11) | (4 << 6) | 4);   // HW_ID.SIMD_ID
-    const float hm = J.dyn.hm;
+    if (DBG && (tid & 63) == 0 && (debug & 2)) s_simd[tid >> 6] = (int)__builtin_amdgcn_s_getreg((1 << 11) | (4 << 6) | 4);   // HW_ID.SIMD_ID
+    const float hm = HEUR ? J.dyn.hm : 0.0f;                  // (the host takes a form without the term when it is 0)
     const int thr = J.dyn.thr, focused = J.dyn.focused;
     // ---- 0. Everything the kernel needs from memory is asked for FIRST, before anything is waited for (round 4: as five dependent steps --
     // cost bytes, patch bytes from host memory, the seeding's returning atomics, the start elements' values behind the step bookkeeping's
@@ -544,6 +557,7 @@ __global__ __launch_bounds__(NTHR) void k_replan_region(DevParams P, RegionJobs 
     STAMP(5);
     for (int i = tid; i < 2 * RTMAX * RTMAX; i += NTHR) (&S.dprio[0][0])[i] = INFBITS;
     for (int i = tid; i < RFRAME; i += NTHR) { S.actL[i] = INFBITS; S.actR[i] = INFBITS; }
+    for (int i = tid; i < 16 * RWW * 32; i += NTHR) (&S.pkey[0][0])[i] = INFBITS;
     if (tid == 0) { S.rmin = INFBITS; S.m_r = INFBITS; }
     {   // pending seeds of this map (all consumed): tiles inside the block are handled here, any other goes to the queue
         // (n_pending was read before the patches of this job were seeded: the general seeding above appends to the list)
@@ -564,7 +578,7 @@ __global__ __launch_bounds__(NTHR) void k_replan_region(DevParams P, RegionJobs 
             float key = 0.0f, dist = 0.0f;
             int off = -1;
             if (se_x >= 0) {
-                dist = hm * hypotf(J.rb.sb.sx - (float)se_x, J.rb.sb.sy - (float)se_y);
+                if (HEUR) dist = hm * hypotf(J.rb.sb.sx - (float)se_x, J.rb.sb.sy - (float)se_y);
                 if (sg < INFINITY) key = sg + dist;
                 if (se_x >= rx0 && se_x < rx0 + rnx && se_y >= ry0 && se_y < ry0 + rny) off = (se_x - rx0 + 1) * RP + (se_y - ry0 + 1);
             }
@@ -581,7 +595,7 @@ __global__ __launch_bounds__(NTHR) void k_replan_region(DevParams P, RegionJobs 
         }
     }
 
-    if (tid == 0) { S.tstamp[0] = t_begin; S.tstamp[1] = wall_clock64(); S.tstamp[2] = S.tstamp[1]; }
+    if (DBG && tid == 0) { S.tstamp[0] = t_begin; S.tstamp[1] = wall_clock64(); S.tstamp[2] = S.tstamp[1]; }
     // the seeds: every patch that holds an element of a consumed rectangle (a superset of the changed cells' elements;
     // a sweep that finds nothing to do costs a fraction of a microsecond)
     __syncthreads();
@@ -605,7 +619,7 @@ __global__ __launch_bounds__(NTHR) void k_replan_region(DevParams P, RegionJobs 
     // ---- 2. invalidate, lower; again while an invalidation that was held back lies below the start's new key ----
     for (int round = 0;; ++round) {
         for (;;) {
-            region_phase<ALGOF, MODE_RAISE>(P, J, Gs, Cb, Bb, S, thr, hm, focused, goal_lx, goal_ly);
+            region_phase<ALGOF, MODE_RAISE, FORM>(P, J, Gs, Cb, Bb, S, thr, hm, focused, goal_lx, goal_ly);
             // a tile that lost a value after some of its patches had been held back: those patches again
             const int again_t = __syncthreads_or(tid < ntl && S.traised[tid] && S.dprio[1][tid] != INFBITS) && !S.giveup;
             __syncthreads();
@@ -614,7 +628,7 @@ __global__ __launch_bounds__(NTHR) void k_replan_region(DevParams P, RegionJobs 
             for (int i = tid; i < RTMAX * RTMAX; i += NTHR) S.dprio[1][i] = INFBITS;
             __syncthreads();
         }
-        if (tid == 0 && round == 0) S.tstamp[3] = wall_clock64();
+        if (DBG && tid == 0 && round == 0) S.tstamp[3] = wall_clock64();
         // everything the invalidation swept is re-lowered (plus, in later rounds, what lowering had to hold back)
         for (int i = tid; i < 16 * RWW; i += NTHR) {
             (&S.wake[0][0])[i] |= (&S.ever[0][0])[i] | (&S.defer[0][0][0])[i];
@@ -631,7 +645,10 @@ __global__ __launch_bounds__(NTHR) void k_replan_region(DevParams P, RegionJobs 
         }
         __syncthreads();
         for (int sub = 0;; ++sub) {
-            region_phase<ALGO, MODE_LOWER>(P, J, Gs, Cb, Bb, S, thr, hm, focused, goal_lx, goal_ly);
+            region_phase<ALGO, MODE_LOWER, FORM>(P, J, Gs, Cb, Bb, S, thr, hm, focused, goal_lx, goal_ly);
+            // the smallest key the sub-round leaves held back: over the patches' last bursts (S.pkey)
+            for (int i = tid; i < 16 * RWW * 32; i += NTHR) { const int k = (&S.pkey[0][0])[i]; if (k != INFBITS) atomicMin(&S.dkey, k); }
+            __syncthreads();
             // the start's key may have risen while results were being held back against an earlier value of it
             if (tid == 0) {
                 const float B = focused ? region_lower_bound(Gs, S) : INFINITY;
@@ -647,7 +664,7 @@ __global__ __launch_bounds__(NTHR) void k_replan_region(DevParams P, RegionJobs 
             const int again_l = S.again;
             __syncthreads();                    // (thread 0 overwrites the word below: everyone has read it first)
             if (!again_l) break;
-            if (tid == 0) ++S.dbg[2];
+            if (DBG && tid == 0) ++S.dbg[2];
             for (int i = tid; i < 16 * RWW; i += NTHR) { (&S.wake[0][0])[i] |= (&S.defer[0][0][0])[i]; (&S.defer[0][0][0])[i] = 0; }
             for (int i = tid; i < RTMAX * RTMAX; i += NTHR) S.dprio[0][i] = INFBITS;
             if (tid == 0) S.dkey = INFBITS;
@@ -668,13 +685,13 @@ __global__ __launch_bounds__(NTHR) void k_replan_region(DevParams P, RegionJobs 
         const int again_r = S.again;
         __syncthreads();
         if (!again_r) break;
-        if (tid == 0) ++S.dbg[3];
+        if (DBG && tid == 0) ++S.dbg[3];
         for (int i = tid; i < 16 * RWW; i += NTHR) { (&S.wake[0][0])[i] |= (&S.defer[1][0][0])[i]; (&S.defer[1][0][0])[i] = 0; }
         for (int i = tid; i < RTMAX * RTMAX; i += NTHR) S.dprio[1][i] = INFBITS;
         __syncthreads();
     }
 
-    if (tid == 0) S.tstamp[4] = wall_clock64();
+    if (DBG && tid == 0) S.tstamp[4] = wall_clock64();
     // ---- 3. write back: changed values, the rings of the neighbours they border, what the frame has to hear ----
     // frame tile index of the tile at block coordinates (ti, tj), ti in -1..ntx, tj in -1..nty (one of them outside)
     auto frame_index = [&](int ti, int tj) {
@@ -803,7 +820,7 @@ __global__ __launch_bounds__(NTHR) void k_replan_region(DevParams P, RegionJobs 
     if (J.batch) __threadfence(); else __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __syncthreads();
 
-    if (tid == 0) S.tstamp[5] = wall_clock64();
+    if (DBG && tid == 0) S.tstamp[5] = wall_clock64();
     // ---- 4. the device-side end condition (as k_replan_end): is anything left below the start's key? ----
     if (tid == 0) { S.m_r = INFBITS; S.m_l = INFBITS; }
     __syncthreads();
@@ -877,7 +894,7 @@ __global__ __launch_bounds__(NTHR) void k_replan_region(DevParams P, RegionJobs 
                 atomicAdd(&P.ctr->elem_evals, 16ull * S.sweeps);
                 if (done) atomicAdd(&P.ctr->expanded, (unsigned long long)S.expanded);
             }
-            if (J.debug & 2) {   // diagnostics: the end check's inputs, readable through ufm_debug_lmax
+            if (DBG && (debug & 2)) {   // diagnostics: the end check's inputs, readable through ufm_debug_lmax
                 int nd0 = 0, nd1 = 0, m0 = INFBITS, m1 = INFBITS;
                 for (int i = 0; i < ntl; ++i) { if (S.dprio[0][i] != INFBITS) { ++nd0; m0 = min(m0, S.dprio[0][i]); } if (S.dprio[1][i] != INFBITS) { ++nd1; m1 = min(m1, S.dprio[1][i]); } }
                 int *d = P.lmax;
@@ -944,7 +961,7 @@ __global__ __launch_bounds__(NTHR) void k_replan_region(DevParams P, RegionJobs 
         //  the L2 back once)
         __syncthreads();
         if (tid == 0) {
-            if (J.debug & 2) P.lmax[37] = (int)(wall_clock64() - S.tstamp[0]);
+            if (DBG && (debug & 2)) P.lmax[37] = (int)(wall_clock64() - S.tstamp[0]);
             __hip_atomic_store(flag, J.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
         }
     }
@@ -994,7 +1011,7 @@ __global__ __launch_bounds__(NTHR) void k_replan_region(DevParams P, RegionJobs 
     }
     // diagnostics: the kernel's end (read behind a stream synchronisation: ufm_debug_lmax).  A batch: every workgroup stamps the same word, the
     // last writer stays -- the end of some workgroup's tail, next to the publisher's "flag at"
-    if (J.debug & 2) {
+    if (DBG && (debug & 2)) {
         __syncthreads();
         if (tid == 0) P.lmax[38] = (int)(wall_clock64() - S.tstamp[0]);
     }
