@@ -54,6 +54,7 @@ namespace {
 #include "ufm_layers.h"
 
 #include "ufm_host.h"
+#include "ufm_map_host.h"
 #include "ufm_delta.h"
 
 }  // namespace
@@ -235,14 +236,6 @@ int ufm_batch_check_layout(ufm_batch_t *b, uint64_t *bad_ring, uint64_t *bad_cos
     if (bad_cost) *bad_cost = c;
     return UFM_OK;
 }
-static int engine_read_map(Engine *e, int m, uint8_t *host_map) {
-    if (!e || !host_map || !e->allocated || m < 0 || m >= e->nmaps) return UFM_ERR_INVALID;
-    HIPCHK(hipSetDevice(e->device));
-    { int rc = e->flush_deferred(); if (rc != UFM_OK) return rc; }
-    HIPCHK(hipMemcpyAsync(host_map, e->P.cost + (size_t)m * e->P.cstride, e->P.cstride, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return UFM_OK;
-}
 int ufm_read_map(ufm_t *p, uint8_t *host_map) { return p ? engine_read_map(p->e, 0, host_map) : UFM_ERR_INVALID; }
 int ufm_set_cspace(ufm_t *p, const uint8_t *mask, int mw, int mh, int anchor_row, int anchor_col) { return p ? engine_set_cspace(p->e, mask, mw, mh, anchor_row, anchor_col) : UFM_ERR_INVALID; }
 int ufm_read_raw_map(ufm_t *p, uint8_t *host_map) { return p ? engine_read_raw_map(p->e, 0, host_map) : UFM_ERR_INVALID; }
@@ -319,9 +312,9 @@ int ufm_track_costs(ufm_t *p, int enable) { return p ? engine_track_costs(p->e, 
 int ufm_read_cost_census(ufm_t *p, uint64_t hist[256], int *min_cost, int *max_cost) { return p ? census_sum(&p->e, 1, 0, 1, hist, min_cost, max_cost) : UFM_ERR_INVALID; }
 int ufm_heuristic_multiplier(ufm_t *p, float *used) { if (!p || !used) return UFM_ERR_INVALID; *used = p->e->last_multiplier; return UFM_OK; }
 int ufm_set_sensor(ufm_t *p, const uint8_t *mask, int mw, int mh, int anchor_row, int anchor_col) { return p ? engine_set_sensor(p->e, mask, mw, mh, anchor_row, anchor_col) : UFM_ERR_INVALID; }
-int ufm_set_survey(ufm_t *p, const uint8_t *host_survey, int width, int length) { return p ? engine_set_survey(p->e, 0, host_survey, false, width, length) : UFM_ERR_INVALID; }
-int ufm_set_survey_device(ufm_t *p, const uint8_t *dev_survey, int width, int length) { return p ? engine_set_survey(p->e, 0, dev_survey, true, width, length) : UFM_ERR_INVALID; }
-int ufm_read_survey(ufm_t *p, uint8_t *host_survey) { return p ? engine_read_survey(p->e, 0, host_survey) : UFM_ERR_INVALID; }
+int ufm_set_survey(ufm_t *p, const uint8_t *host_survey, int width, int length) { return p ? engine_set_layer_survey(p->e, 0, 0, host_survey, false, width, length) : UFM_ERR_INVALID; }
+int ufm_set_survey_device(ufm_t *p, const uint8_t *dev_survey, int width, int length) { return p ? engine_set_layer_survey(p->e, 0, 0, dev_survey, true, width, length) : UFM_ERR_INVALID; }
+int ufm_read_survey(ufm_t *p, uint8_t *host_survey) { return p ? engine_read_layer_survey(p->e, 0, 0, host_survey, false) : UFM_ERR_INVALID; }
 int ufm_reveal(ufm_t *p, int row, int col, uint64_t *changed) {
     if (!p) return UFM_ERR_INVALID;
     const int32_t c[2] = {row, col};
@@ -504,8 +497,8 @@ int ufm_batch_set_sensor(ufm_batch_t *b, const uint8_t *mask, int mw, int mh, in
     for (Engine *e : b->shards) { const int rc = engine_set_sensor(e, mask, mw, mh, anchor_row, anchor_col); if (rc != UFM_OK) return rc; }
     return UFM_OK;
 }
-int ufm_batch_set_survey(ufm_batch_t *b, int i, const uint8_t *host_survey, int width, int length) { UFM_BATCH_MAP(b, i); return engine_set_survey(e, li, host_survey, false, width, length); }
-int ufm_batch_set_survey_device(ufm_batch_t *b, int i, const uint8_t *dev_survey, int width, int length) { UFM_BATCH_MAP(b, i); return engine_set_survey(e, li, dev_survey, true, width, length); }
+int ufm_batch_set_survey(ufm_batch_t *b, int i, const uint8_t *host_survey, int width, int length) { UFM_BATCH_MAP(b, i); return engine_set_layer_survey(e, li, 0, host_survey, false, width, length); }
+int ufm_batch_set_survey_device(ufm_batch_t *b, int i, const uint8_t *dev_survey, int width, int length) { UFM_BATCH_MAP(b, i); return engine_set_layer_survey(e, li, 0, dev_survey, true, width, length); }
 int ufm_batch_set_image(ufm_batch_t *b, int i, const uint8_t *host_image, int width, int length, const uint16_t *taps, int ntaps, int penalty) {
     UFM_BATCH_MAP(b, i);
     return engine_set_image(e, li, host_image, false, width, length, taps, ntaps, penalty);
@@ -514,7 +507,7 @@ int ufm_batch_set_image_device(ufm_batch_t *b, int i, const uint8_t *dev_image, 
     UFM_BATCH_MAP(b, i);
     return engine_set_image(e, li, dev_image, true, width, length, taps, ntaps, penalty);
 }
-int ufm_batch_read_survey(ufm_batch_t *b, int i, uint8_t *host_survey) { UFM_BATCH_MAP(b, i); return engine_read_survey(e, li, host_survey); }
+int ufm_batch_read_survey(ufm_batch_t *b, int i, uint8_t *host_survey) { UFM_BATCH_MAP(b, i); return engine_read_layer_survey(e, li, 0, host_survey, false); }
 int ufm_batch_set_layers(ufm_batch_t *b, int n) {
     if (!b || b->shards.empty() || !layers_count_ok(n)) return UFM_ERR_INVALID;
     for (Engine *e : b->shards) for (const MapState &ms : e->maps) if (ms.have_map) return UFM_ERR_INVALID;   // (all shards or none)

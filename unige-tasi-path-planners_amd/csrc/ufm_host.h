@@ -1,4 +1,7 @@
-// ufm_host.h -- the host side: Engine (allocation, launch chain, resident phase, replan submission, ReplannerBase::step)
+// ufm_host.h -- the host side of planning: Engine (its members, allocation, launch chain, resident phase, replan submission,
+// ReplannerBase::step), creation and destruction, the goal, field reads, path extraction, queue and back-pointer reads.  Keeping the
+// raster -- patches, footprint, census, surveys and reveals, layers, images -- is ufm_map_host.h; the step code uses flush_deferred(),
+// lazy, h_lazy and pending of it.
 // (a piece of ufm_engine.hip, the engine's one translation unit: included there, inside its anonymous namespace)
 #pragma once
 
@@ -10,6 +13,7 @@
     } while (0)
 
 #include "ufm_route.h"
+#include "ufm_patch_route.h"
 #include "ufm_path.h"
 
 static_assert(RJOBS <= ROUTE_MAX_JOBS && RTMAX >= 3, "ufm_route.h places at most ROUTE_MAX_JOBS blocks");
@@ -55,6 +59,19 @@ template <class P> int regrow(hipStream_t s, size_t bytes, size_t &cap, size_t n
 }
 
 template <class... Q> void free_all(hipError_t (*release)(void *), Q *...q) { ((q ? (void)release(q) : (void)0), ...); }
+
+// A grow-only scratch buffer of bytes (regrow above): reserve() leaves at least `bytes` of capacity, never fewer than 4096 once there is any;
+// `twin`: with a pinned buffer of the same size.  A buffer that grows is a new one: what was queued on the old one has been waited for.
+struct GrowBuf {
+    uint8_t *dev = nullptr, *pinned = nullptr;
+    size_t cap = 0;
+    int reserve(hipStream_t s, size_t bytes, bool twin = false) {
+        if (bytes <= cap) return UFM_OK;
+        const size_t n = std::max<size_t>(bytes, 4096);
+        return regrow(s, n, cap, n, dev, twin ? &pinned : nullptr);
+    }
+    void release() { free_all(hipFree, dev); free_all(hipHostFree, pinned); dev = pinned = nullptr; cap = 0; }
+};
 
 struct Engine {
     int algo = 0, opt_lvl = 0, heur = 0, device = 0, nmaps = 1;
@@ -131,15 +148,10 @@ struct Engine {
         }
     } scratch;
     int *d_scratch = nullptr;
-    uint8_t *d_patch = nullptr;      // staging for host patches
-    size_t d_patch_cap = 0;
-    uint8_t *h_patch = nullptr;      // pinned staging
     float *d_field = nullptr;        // ufm_read_field: the requested window, dense
     size_t d_field_cap = 0;
     int32_t *d_info = nullptr;       // ufm_read_info: back-pointers of the requested window
     size_t d_info_cap = 0;           // (int32 entries)
-    uint8_t *d_pmask = nullptr;      // changed-cell mask of the patch being applied
-    size_t d_pmask_cap = 0;
     PathJob *d_jobs = nullptr, *h_jobs = nullptr;     // path extraction: the walks of one launch (h_: pinned)
     size_t jobs_cap = 0;                              // jobs per buffer
     float *d_path = nullptr, *h_path = nullptr;       // per-job output records
@@ -225,21 +237,36 @@ struct Engine {
     int seed_only(StepRun &r);
     int converge(StepRun &r);
     void copy_counters(ufm_stats &st) const;
-    int patch(int m, const uint8_t *dev_patch, int x, int y, int w, int h, bool may_defer = false);
-    // OPT-IN (ufm_batch_set_param "defer_patches", 1; round 4: it was the default, which silently extended the lifetime the ABI asks of
-    // a patch buffer): small patches handed to a batch as device pointers are held back until something needs them applied (the next
-    // step, a read of the raster, a path extraction) and applied by ONE launch -- the caller then keeps each buffer valid and unchanged
+
+    // ---- the map side: keeping the raster (ufm_map_host.h has the functions).  Of all this the step code above uses flush_deferred(),
+    // lazy, h_lazy and pending.  Every patch -- the caller's host or device bytes, a reveal's slot, a layer patch -- goes through
+    // route_patch(), which acts on what plan_patch (ufm_patch_route.h) says: held, deferred or applied.
+    PatchSwitches patch_switches(int m) const;
+    PatchPlan patch_plan(PatchSource source, bool host_bytes, int k, const PatchRect &r) const;
+    int patch_room(const PatchPlan &p);
+    int route_patch(PatchSource source, bool host_bytes, int k, const uint8_t *bytes, const PatchRect &r);
+    int stage_host_patch(const uint8_t *src, size_t n);
+    GrowBuf d_patch;                 // staging for host patches, with its pinned twin
+    GrowBuf d_pmask;                 // changed-cell mask of the patch being applied
+    int ensure_pmask(size_t need);
+    void patch_small(int m, const uint8_t *src, int x, int y, int w, int h) {
+        with_elements(algo, [&](auto nodes) { k_patch_small<nodes()><<<1, 1024, 0, stream>>>(P, m, src, d_pmask.dev, x, y, w, h); });
+    }
+    // Deferred -- OPT-IN (ufm_batch_set_param "defer_patches", 1; round 4: it was the default, which silently extended the lifetime the ABI
+    // asks of a patch buffer): small patches handed to a batch as device pointers are held back until something needs them applied (the
+    // next step, a read of the raster, a path extraction) and applied by ONE launch -- the caller then keeps each buffer valid and unchanged
     // until that call has returned.  Off: every patch is applied at the call, stream-ordered, like a single planner's.
     struct DeferredPatch { int m, x, y, w, h; const uint8_t *ptr; };
     std::vector<DeferredPatch> deferred;
     bool defer_patches = false;
-    int flush_deferred();
+    int flush_deferred();            // everything that is being held or deferred, applied
     int flush_deferred_only();
-    // A small patch of a SINGLE planner handed over from HOST memory (ufm_patch_map) is not uploaded and applied at the call: its bytes are
-    // copied into a slot of host-coherent pinned memory (the caller's buffer is free again when the call returns, as before) and the replan's
-    // block kernel reads them from there and does Graph::update + the seeding itself (RegionJob::psrc) -- no staging copy, no stream
-    // synchronisation, no patch kernel in front of the replan.  Whatever else needs the raster first (a read of the map, a path extraction,
-    // another kind of patch, a step that does not go through the block kernel) applies the held patches the ordinary way: flush_lazy().
+    // Held -- a small patch of a SINGLE planner handed over from HOST memory (ufm_patch_map) is not uploaded and applied at the call: its
+    // bytes are copied into a slot of host-coherent pinned memory (the caller's buffer is free again when the call returns, as before) and
+    // the replan's block kernel reads them from there and does Graph::update + the seeding itself (RegionJob::psrc) -- no staging copy, no
+    // stream synchronisation, no patch kernel in front of the replan.  Whatever else needs the raster first (a read of the map, a path
+    // extraction, another kind of patch, a step that does not go through the block kernel) applies the held patches the ordinary way:
+    // flush_lazy().
     static constexpr int LAZY_SLOTS = 4;                  // = the most rectangles a block-kernel job takes
     struct LazyPatch { int m, x, y, w, h, slot; };
     std::vector<LazyPatch> lazy;
@@ -247,27 +274,19 @@ struct Engine {
     int lazy_next = 0;               // slot after the last one handed out
     bool lazy_dirty[LAZY_SLOTS] = {false, false, false, false};   // a kernel queued on the stream may still read the slot
     bool lazy_patches = true;
-    int patch_lazy(int m, const uint8_t *host_patch, int x, int y, int w, int h, bool *taken);
+    int hold_host_patch(const PatchRect &r, const uint8_t *host_patch);
     int flush_lazy();
-    int ensure_pmask(size_t n);
-    // C-space inflation (ufm_set_cspace; ufm_cspace.h).  Off -- the default, and a 1 x 1 mask -- nothing below exists or runs.
-    // On: d_raw holds the caller's raster per map, P.cost its dilation by the footprint; a raw patch goes to d_raw, the rectangle of P.cost it
-    // can change is dilated into d_cs_patch and handed to patch() as an ordinary patch -- never held for the block kernel, never deferred,
-    // both of which would apply raw bytes to the planning raster.
+    // C-space inflation (ufm_set_cspace; ufm_cspace.h).  Off -- the default, and a 1 x 1 mask -- nothing below exists
+    // or runs.  On: d_raw holds the caller's raster per map, P.cost its dilation by the footprint; a raw patch goes to d_raw, the rectangle
+    // of P.cost it can change is dilated into d_cs_patch and that one is applied as an ordinary patch.
     CspaceMask cs;
     uint8_t *d_raw = nullptr;        // [nmaps][L][W]
-    uint8_t *d_cs_patch = nullptr;   // the dilated grown rectangle of the patch being applied, dense
-    size_t d_cs_patch_cap = 0;
+    GrowBuf d_cs_patch;              // the dilated grown rectangle of the patch being applied, dense
     void cspace_dilate(int m, uint8_t *out, int pitch, const PatchRect &r);
-    int patch_raw(int m, const uint8_t *dev_patch, int x, int y, int w, int h);
-    void patch_small(int m, const uint8_t *src, int x, int y, int w, int h) {
-        with_elements(algo, [&](auto nodes) { k_patch_small<nodes()><<<1, 1024, 0, stream>>>(P, m, src, d_pmask, x, y, w, h); });
-    }
     // Cost census (ufm_track_costs; ufm_census.h).  Off -- the default -- nothing below exists or runs.  On: d_census
     // holds, per map, how many cells of P.cost have each value, exactly, between any two calls: built after the raster is final
-    // (engine_set_map), corrected in front of every patch kernel (patch()) -- and the two routes that apply a patch later, the block kernel's
-    // held host patches and a batch's deferred device patches, are declined, as with a footprint.  After every build or patch the smallest
-    // and largest value present are published to h_cen; "auto_multiplier" makes a step take that minimum as its heuristic multiplier.
+    // (engine_new_raster), corrected in front of every patch kernel.  After every build or patch the smallest and largest value present
+    // are published to h_cen; "auto_multiplier" makes a step take that minimum as its heuristic multiplier.
     bool census_on = false, auto_multiplier = false;
     uint32_t *d_census = nullptr;    // [nmaps][256]
     int *h_cen = nullptr;            // pinned, host-coherent: {min, max} over the engine's maps ...
@@ -279,55 +298,47 @@ struct Engine {
     void census_publish() { k_census_publish<<<1, CENSUS_BINS, 0, stream>>>(d_census, nmaps, h_cen, h_cen_flag, ++cen_seq); }
     int census_minmax(int *mn, int *mx);
     void census_free();
-    // Sensor reveal (ufm_set_sensor / ufm_set_survey / ufm_reveal; ufm_sensor.h).  No sensor and no survey -- the default --
-    // nothing below exists or runs.  d_survey holds what the sensor would see, per map; a reveal makes the dense patch Q of every map's field
-    // of view in ONE launch (k_reveal) into that map's slot of d_reveal and hands the slot to patch_raw() / patch() as the caller's device
-    // patch would be handed -- so whatever a patch does (raw store, re-dilation, census, seeding, the block kernel, deferral) a reveal does.
-    // A deferred patch may point into d_reveal: reveal() applies what is held before k_reveal writes the slots again.
+    // Sensor reveal (ufm_set_sensor / ufm_set_survey / ufm_reveal; ufm_sensor.h).  No sensor and no survey -- the
+    // default -- nothing below exists or runs.  d_lsurvey[k] holds what the sensor would see of layer k, per map (one layer: k = 0, the
+    // map); a reveal makes the dense patch Q of every map's field of view in ONE launch (k_reveal, k_reveal_layers with more than one
+    // layer) into that map's slot of d_reveal and hands the slot to route_patch().  A deferred patch may point into d_reveal: reveal()
+    // applies what is held before the kernel writes the slots again.
     SensorShape sensor;
     uint8_t *d_sensor = nullptr;     // the mask's bytes, room for SENSOR_MAX^2
-    uint8_t *d_survey = nullptr;     // [nmaps][L][W]; dropped with the rasters (release())
-    std::vector<uint8_t> have_survey;    // [nmaps]
-    uint8_t *d_reveal = nullptr;     // [nmaps] slots of sensor_slot_stride() bytes
-    size_t d_reveal_cap = 0;
+    uint8_t *d_lsurvey[LAYERS_MAX] = {nullptr, nullptr, nullptr, nullptr};   // [nmaps][L][W] each; dropped with the rasters (release())
+    std::vector<uint8_t> have_lsurvey[LAYERS_MAX];   // [nmaps] each
+    int survey_alloc(int k);
+    GrowBuf d_reveal;                // [nmaps] slots of sensor_slot_stride() bytes
     unsigned int *d_reveal_cnt = nullptr;    // [nmaps]: changed cells of the last reveal
-    int32_t *h_centres = nullptr;    // [nmaps][2], pinned + mapped: k_reveal reads the centres from here
-    bool reveal_busy = false;        // a k_reveal that is only queued may still read h_centres
+    int32_t *h_centres = nullptr;    // [3 * nmaps], pinned + mapped: the centres as the reveal kernel reads them ([nmaps][2], with layers [nmaps][3])
+    bool reveal_busy = false;        // a reveal kernel that is only queued may still read h_centres
     int reveal_check(const int32_t *centres) const;
     int reveal(const int32_t *centres);
     int reveal_counts(const int32_t *centres, uint64_t *changed);
-    // Map preparation (ufm_set_image; ufm_prepare.h).  Never called -- the default -- nothing below exists.  k_prepare must not
-    // read what it writes: a host bitmap, or a device bitmap that overlaps the rasters, goes through this buffer, which is the engine's and
-    // reused by every map, not kept per map.
-    uint8_t *d_image = nullptr;
-    size_t d_image_cap = 0;
+    // Map preparation (ufm_set_image; ufm_prepare.h).  Never called -- the default -- nothing below exists.  k_prepare
+    // must not read what it writes: a host bitmap, or a device bitmap that overlaps the rasters, goes through this buffer, which is the
+    // engine's and reused by every map, not kept per map.
+    GrowBuf d_image;
     hipEvent_t prep_ev[2] = {nullptr, nullptr};   // profiling: on the k_prepare dispatch itself
     float prep_ms = 0.0f;            // ... its duration (tools/prepare_probe.py)
     // Cost layers (ufm_set_layers / ufm_patch_layer / ufm_set_layer; ufm_layers.h).  n_layers == 1 -- the default --
     // nothing below exists or runs.  With more, d_layers holds n rasters per map and the caller's raster (d_raw with a footprint, P.cost
     // without) is their element-wise maximum between any two calls: a layer patch is stored, composed over its rectangle into the dense
-    // d_lcomp and that one goes to patch_raw() / patch() as the caller's device patch would -- never held for the block kernel, never
-    // deferred, both of which would put one layer's bytes into the composed raster.  Layer 0's survey is d_survey; layers 1 .. n-1 have
-    // d_lsurvey[k], and a reveal uncovers every layer that has one in ONE launch (k_reveal_layers).
+    // d_lcomp and that one goes on as the caller's device patch would.  A reveal uncovers every layer that has a survey.
     int n_layers = 1;
     uint8_t *d_layers = nullptr;     // [n_layers][nmaps] rasters at lstride bytes; dropped with the rasters (release())
     size_t lstride = 0;
-    uint8_t *d_lsurvey[LAYERS_MAX] = {nullptr, nullptr, nullptr, nullptr};   // [nmaps][L][W] each ([0] stays null: d_survey); dropped with the rasters
-    std::vector<uint8_t> have_lsurvey[LAYERS_MAX];   // [nmaps] each
-    uint8_t *d_lcomp = nullptr;      // the dense composed patch of the layer call being applied
-    size_t d_lcomp_cap = 0;
-    int32_t *h_lcentres = nullptr;   // [nmaps][3], pinned + mapped: k_reveal_layers reads centres and survey bits from here
+    GrowBuf d_lcomp;                 // the dense composed patch of the layer call being applied
     hipEvent_t lay_ev[2] = {nullptr, nullptr};   // profiling: on the dispatch of the last layer kernel
     bool lay_timed = false;
     uint8_t *layer_ptr(int k, int m) const { return d_layers + layers_slot(k, m, nmaps, lstride); }
     int layer_surveys(int m) const {             // bit k: layer k of map m has a survey
-        int have = (d_survey && (size_t)m < have_survey.size() && have_survey[m]) ? 1 : 0;
-        for (int k = 1; k < n_layers; ++k) if (d_lsurvey[k] && (size_t)m < have_lsurvey[k].size() && have_lsurvey[k][m]) have |= 1 << k;
+        int have = 0;
+        for (int k = 0; k < n_layers; ++k) if (d_lsurvey[k] && (size_t)m < have_lsurvey[k].size() && have_lsurvey[k][m]) have |= 1 << k;
         return have;
     }
     int layer_events(hipEvent_t *e0, hipEvent_t *e1);
-    int patch_layer(int m, int k, const uint8_t *dev_patch, int x, int y, int w, int h);
-    int reveal_layers(const int32_t *centres);
+    int compose_layer(int k, const uint8_t *dev_patch, const PatchRect &r);
     // step deltas (ufm_track_changes / ufm_read_changes, ufm_delta.h): nothing below exists unless a caller turned tracking on
     bool track = false;
     float *trk_g = nullptr;          // the baseline: the field as the caller was last told, in the layout of P.G (same gstride)
@@ -355,12 +366,9 @@ void Engine::release() {
     for (void *q : ptrs) if (q) hipFree(q);
     if (d_raw) hipFree(d_raw);
     d_raw = nullptr;
-    if (d_survey) hipFree(d_survey);     // (a survey belongs to rasters of these dimensions)
-    d_survey = nullptr;
-    std::fill(have_survey.begin(), have_survey.end(), (uint8_t)0);
-    if (d_layers) hipFree(d_layers);     // (the layers and their surveys: rasters of these dimensions too)
+    if (d_layers) hipFree(d_layers);     // (the layers: rasters of these dimensions too)
     d_layers = nullptr;
-    for (int k = 0; k < LAYERS_MAX; ++k) {
+    for (int k = 0; k < LAYERS_MAX; ++k) {   // (a survey belongs to rasters of these dimensions)
         if (d_lsurvey[k]) hipFree(d_lsurvey[k]);
         d_lsurvey[k] = nullptr;
         std::fill(have_lsurvey[k].begin(), have_lsurvey[k].end(), (uint8_t)0);
@@ -722,329 +730,6 @@ int Engine::run_phase(int mode, float rbound, uint32_t *launches, float *kernel_
         batch = batch_fixed > 0 ? batch_fixed : (active > 512 ? 32 : (active > 256 ? 16 : (active > 32 ? 8 : 4)));
         prev = cur;
     }
-}
-
-int Engine::flush_deferred() {       // every patch that is being held -- a single planner's host patches, a batch's deferred device patches -- applied
-    { int rc = flush_lazy(); if (rc != UFM_OK) return rc; }
-    return flush_deferred_only();
-}
-int Engine::flush_deferred_only() {
-    if (deferred.empty()) return UFM_OK;
-    PatchMulti a{};
-    a.n = (int)deferred.size();
-    for (int i = 0; i < a.n; ++i) {
-        const DeferredPatch &d = deferred[i];
-        put_rect(a.rect[i], PatchRect{d.m, d.x, d.y, d.w, d.h});
-        a.ptr[i] = d.ptr;
-    }
-    deferred.clear();
-    with_elements(algo, [&](auto nodes) { k_patch_multi<nodes()><<<a.n, 1024, 0, stream>>>(P, a, d_pmask); });
-    HIPCHK(hipGetLastError());
-    return UFM_OK;
-}
-
-int Engine::ensure_pmask(size_t n) {   // room for the masks of PATCH_MULTI small patches, or of one large one
-    const size_t need = std::max((size_t)PATCH_MULTI * 4096, n);
-    if (need > d_pmask_cap) {
-        { int rc = flush_deferred_only(); if (rc != UFM_OK) return rc; }      // (their launch writes the old buffer)
-        { int rc = regrow(stream, need, d_pmask_cap, need, d_pmask); if (rc != UFM_OK) return rc; }
-    }
-    return UFM_OK;
-}
-// the held host patches, applied the ordinary way (one k_patch_small each, reading the pinned slot), in the order they came
-int Engine::flush_lazy() {
-    if (lazy.empty()) return UFM_OK;
-    { int rc = ensure_pmask(4096); if (rc != UFM_OK) return rc; }
-    for (const LazyPatch &p : lazy) {
-        patch_small(p.m, h_lazy + (size_t)p.slot * 4096, p.x, p.y, p.w, p.h);
-        lazy_dirty[p.slot] = true;         // (read by a kernel that is only queued: patch_lazy waits for the stream before it writes the slot again)
-    }
-    lazy.clear();
-    HIPCHK(hipGetLastError());
-    return UFM_OK;
-}
-// ufm_patch_map of a small patch, single planner: hold it (see the member's comment); *taken = false: the caller goes the ordinary way
-int Engine::patch_lazy(int m, const uint8_t *host_patch, int x, int y, int w, int h, bool *taken) {
-    *taken = false;
-    if (m < 0 || m >= nmaps || !allocated || !maps[m].have_map) return UFM_ERR_INVALID;
-    if (x < 0 || y < 0 || w <= 0 || h <= 0 || x + h > L || y + w > W) return UFM_ERR_INVALID;   // Graph.cpp:38-41
-    if (cs.on) return UFM_OK;          // (a footprint: the block kernel would apply raw bytes to the planning raster)
-    if (census_on) return UFM_OK;      // (the census: the block kernel would change the raster behind the counters' back)
-    if (n_layers > 1) return UFM_OK;   // (layers: the block kernel would put one layer's bytes into the composed raster)
-    if (!(lazy_patches && nmaps == 1 && use_region && fuse_control && spin_wait && w <= 64 && h <= 64)) return UFM_OK;
-    if ((int)lazy.size() >= LAZY_SLOTS || pending.size() != lazy.size()) return UFM_OK;      // (only behind other held patches: the block kernel applies them in order)
-    if (!h_lazy) HIPCHK(hipHostMalloc(&h_lazy, (size_t)LAZY_SLOTS * 4096, hipHostMallocMapped));
-    // (a slot is free again when the step that consumed its patch has returned -- step() is synchronous -- or when flush_lazy() has run and the
-    //  stream has been waited for; slots are handed out in order, so the one after the last held patch's is the oldest)
-    const int slot = lazy.empty() ? (lazy_next % LAZY_SLOTS) : ((lazy.back().slot + 1) % LAZY_SLOTS);
-    if (lazy_dirty[slot]) { HIPCHK(hipStreamSynchronize(stream)); for (bool &d : lazy_dirty) d = false; }
-    std::memcpy(h_lazy + (size_t)slot * 4096, host_patch, (size_t)w * h);
-    __atomic_thread_fence(__ATOMIC_RELEASE);
-    lazy.push_back({m, x, y, w, h, slot});
-    lazy_next = slot + 1;
-    pending.push_back({m, x, y, w, h});
-    *taken = true;
-    return UFM_OK;
-}
-int Engine::patch(int m, const uint8_t *dev_patch, int x, int y, int w, int h, bool may_defer) {
-    if (m < 0 || m >= nmaps || !allocated || !maps[m].have_map) return UFM_ERR_INVALID;
-    if (x < 0 || y < 0 || w <= 0 || h <= 0 || x + h > L || y + w > W) return UFM_ERR_INVALID;   // Graph.cpp:38-41
-    const int n = w * h;
-    { int rc = flush_lazy(); if (rc != UFM_OK) return rc; }       // (held host patches come first)
-    { int rc = ensure_pmask((size_t)n); if (rc != UFM_OK) return rc; }
-    // (a batch only: the patch kernel of a single map runs while the host prepares the step -- applying it inside the
-    //  replan's block kernel instead was tried and saved nothing, it only made that kernel longer)
-    if (may_defer && defer_patches && !census_on && n_layers == 1 && nmaps > 1 && n <= 4096) {
-        // (one per map at a time: two patches of one map may overlap, and then their order counts)
-        bool clash = (int)deferred.size() >= PATCH_MULTI;
-        for (const DeferredPatch &d : deferred) clash = clash || d.m == m;
-        if (clash) { int rc = flush_deferred(); if (rc != UFM_OK) return rc; }
-        deferred.push_back({m, x, y, w, h, dev_patch});
-        pending.push_back({m, x, y, w, h});
-        return UFM_OK;
-    }
-    { int rc = flush_deferred(); if (rc != UFM_OK) return rc; }   // keep the order of the patches
-    if (census_on) { census_patch(m, dev_patch, x, y, w, h); census_publish(); }   // (reads the old bytes: in front of the kernel that overwrites them)
-    if (n <= 4096) {
-        patch_small(m, dev_patch, x, y, w, h);
-    } else {
-        k_patch_apply<<<(n + 255) / 256, 256, 0, stream>>>(P, m, dev_patch, d_pmask, x, y, w, h);
-        const int ne = (w + 1) * (h + 1);
-        with_elements(algo, [&](auto nodes) { k_patch_seed<nodes()><<<(ne + 255) / 256, 256, 0, stream>>>(P, m, d_pmask, x, y, w, h); });
-    }
-    HIPCHK(hipGetLastError());
-    pending.push_back({m, x, y, w, h});
-    return UFM_OK;
-}
-
-// ---- C-space inflation: planning raster == dilate(raw raster), kept at a cost proportional to the patch ----
-void Engine::cspace_dilate(int m, uint8_t *out, int pitch, const PatchRect &r) {
-    CspaceJob j{};
-    j.raw = d_raw + (size_t)m * P.cstride; j.out = out;
-    j.L = L; j.W = W; j.x0 = r.x; j.y0 = r.y; j.h = r.h; j.w = r.w; j.pitch = pitch;
-    j.mh = cs.mh; j.mw = cs.mw; j.ar = cs.ar; j.ac = cs.ac;
-    for (int a = 0; a < CSPACE_MAX; ++a) j.rows[a] = cs.rows[a];
-    k_cspace_dilate<<<dim3((r.w + CS_TC - 1) / CS_TC, (r.h + CS_TR - 1) / CS_TR), 256, 0, stream>>>(j);
-}
-// a raw patch with a footprint set, stream-ordered: into the raw store, the grown rectangle dilated into the scratch patch, that one
-// through patch() -- which detects the cells of the planning raster that really changed, seeds from them and keeps the cost windows in step
-int Engine::patch_raw(int m, const uint8_t *dev_patch, int x, int y, int w, int h) {
-    if (m < 0 || m >= nmaps || !allocated || !maps[m].have_map) return UFM_ERR_INVALID;
-    if (x < 0 || y < 0 || w <= 0 || h <= 0 || x + h > L || y + w > W) return UFM_ERR_INVALID;   // Graph.cpp:38-41
-    const PatchRect g = grow_rect(PatchRect{m, x, y, w, h}, cs.mh, cs.mw, cs.ar, cs.ac, L, W);
-    const size_t n = (size_t)g.w * g.h;
-    if (n > d_cs_patch_cap) {
-        const size_t cap = std::max<size_t>(n, 4096);
-        { int rc = regrow(stream, cap, d_cs_patch_cap, cap, d_cs_patch); if (rc != UFM_OK) return rc; }
-    }
-    // (everything patch() does that can fail -- applying what is held, the mask buffer's growth -- comes before the first write to the raw
-    //  store: a call that returns an error has left both rasters as they were)
-    { int rc = flush_deferred(); if (rc != UFM_OK) return rc; }
-    { int rc = ensure_pmask(n); if (rc != UFM_OK) return rc; }
-    k_raw_store<<<(w * h + 255) / 256, 256, 0, stream>>>(d_raw + (size_t)m * P.cstride, W, dev_patch, x, y, w, h);
-    cspace_dilate(m, d_cs_patch, g.w, g);
-    HIPCHK(hipGetLastError());
-    return patch(m, d_cs_patch, g.x, g.y, g.w, g.h);
-}
-
-// ---- the cost census: hist[v] == number of cells of P.cost with value v, per map ----
-void Engine::census_build(int m) {
-    uint32_t *hist = d_census + (size_t)m * CENSUS_BINS;
-    (void)hipMemsetAsync(hist, 0, sizeof(uint32_t) * CENSUS_BINS, stream);
-    const CensusBuildJob j{P.cost + (size_t)m * P.cstride, P.cstride, hist};
-    k_census_build<<<census_build_grid(census_split(reinterpret_cast<uintptr_t>(j.cost), j.n).nvec), CENSUS_THREADS, 0, stream>>>(j);
-}
-void Engine::census_patch(int m, const uint8_t *dev_patch, int x, int y, int w, int h) {
-    const CensusPatchJob j{P.cost + (size_t)m * P.cstride, dev_patch, d_census + (size_t)m * CENSUS_BINS, W, x, y, w, h};
-    k_census_patch<<<census_patch_grid(w * h), CENSUS_THREADS, 0, stream>>>(j);
-}
-// the published range as of the last build or patch queued: the host waits for that copy's sequence number (nothing is held while the census is on)
-int Engine::census_minmax(int *mn, int *mx) {
-    if (!census_on) return UFM_ERR_INVALID;
-    { int rc = wait_flag(h_cen_flag, cen_seq); if (rc != UFM_OK) return rc; }
-    *mn = h_cen[0]; *mx = h_cen[1];
-    return UFM_OK;
-}
-void Engine::census_free() {
-    if (d_census) hipFree(d_census);
-    if (h_cen) hipHostFree(h_cen);
-    d_census = nullptr; h_cen = nullptr; h_cen_flag = nullptr;
-    census_on = auto_multiplier = false;
-}
-
-// ---- the sensor reveal: a move uncovers the survey raster's field of view, as a patch made on the device ----
-// everything a reveal of these centres ([nmaps][2], row < 0: skipped) needs; nothing is launched or written
-int Engine::reveal_check(const int32_t *centres) const {
-    if (n_layers > 1) {                  // (layers: any layer's survey will do, every map that is not skipped needs one)
-        if (!centres || !sensor.set || !allocated) return UFM_ERR_INVALID;
-        for (int m = 0; m < nmaps; ++m) {
-            if (centres[2 * m] < 0) continue;
-            if (!maps[m].have_map || !layer_surveys(m) || !sensor_centre_ok(centres[2 * m], centres[2 * m + 1], L, W)) return UFM_ERR_INVALID;
-        }
-        return UFM_OK;
-    }
-    if (!centres || !sensor.set || !allocated || !d_survey) return UFM_ERR_INVALID;
-    for (int m = 0; m < nmaps; ++m) {
-        if (centres[2 * m] < 0) continue;
-        if (!maps[m].have_map || !have_survey[m] || !sensor_centre_ok(centres[2 * m], centres[2 * m + 1], L, W)) return UFM_ERR_INVALID;
-    }
-    return UFM_OK;
-}
-// One k_reveal for all maps, then every map's slot through the route its device patch would take.  As in patch_raw(), whatever can fail
-// -- applying what is held, the growth of the buffers -- comes before the first write to a raster.
-int Engine::reveal(const int32_t *centres) {
-    if (n_layers > 1) return reveal_layers(centres);
-    { int rc = reveal_check(centres); if (rc != UFM_OK) return rc; }
-    bool any = false;
-    for (int m = 0; m < nmaps; ++m) any = any || centres[2 * m] >= 0;
-    if (!any) return UFM_OK;
-    // held patches first, in order -- and a deferred one may point into the slots k_reveal is about to overwrite
-    { int rc = flush_deferred(); if (rc != UFM_OK) return rc; }
-    const size_t stride = sensor_slot_stride(sensor.mw, sensor.mh), need = stride * (size_t)nmaps;
-    if (need > d_reveal_cap) { int rc = regrow(stream, need, d_reveal_cap, need, d_reveal); if (rc != UFM_OK) return rc; }
-    size_t largest = (size_t)sensor.mw * sensor.mh;                       // the largest patch any map's slot can become
-    if (cs.on) {
-        largest = (size_t)(sensor.mw + cs.mw - 1) * (size_t)(sensor.mh + cs.mh - 1);
-        if (largest > d_cs_patch_cap) {
-            const size_t cap = std::max<size_t>(largest, 4096);
-            { int rc = regrow(stream, cap, d_cs_patch_cap, cap, d_cs_patch); if (rc != UFM_OK) return rc; }
-        }
-    }
-    { int rc = ensure_pmask(largest); if (rc != UFM_OK) return rc; }
-    if (reveal_busy) { HIPCHK(hipStreamSynchronize(stream)); reveal_busy = false; }
-    std::memcpy(h_centres, centres, sizeof(int32_t) * 2 * (size_t)nmaps);
-    __atomic_thread_fence(__ATOMIC_RELEASE);
-    HIPCHK(hipMemsetAsync(d_reveal_cnt, 0, sizeof(unsigned int) * nmaps, stream));
-    RevealJob j{};
-    j.mask = d_sensor; j.survey = d_survey; j.cur = cs.on ? d_raw : P.cost; j.slots = d_reveal; j.count = d_reveal_cnt; j.centres = h_centres;
-    j.cstride = P.cstride; j.slot_stride = stride;
-    j.L = L; j.W = W; j.mh = sensor.mh; j.mw = sensor.mw; j.ar = sensor.ar; j.ac = sensor.ac;
-    k_reveal<<<dim3(sensor_grid_x(sensor.mw, sensor.mh), nmaps), SENSOR_THREADS, 0, stream>>>(j);
-    HIPCHK(hipGetLastError());
-    reveal_busy = true;
-    for (int m = 0; m < nmaps; ++m) {
-        if (centres[2 * m] < 0) continue;
-        const SensorRect r = sensor_place(centres[2 * m], centres[2 * m + 1], sensor.mh, sensor.mw, sensor.ar, sensor.ac, L, W);
-        const uint8_t *slot = d_reveal + stride * (size_t)m;
-        const int rc = cs.on ? patch_raw(m, slot, r.x, r.y, r.w, r.h) : patch(m, slot, r.x, r.y, r.w, r.h, true);
-        if (rc != UFM_OK) return rc;
-    }
-    return UFM_OK;
-}
-// the counts of the last reveal, once the stream has run: changed[m], 0 for a map that was skipped
-int Engine::reveal_counts(const int32_t *centres, uint64_t *changed) {
-    std::vector<unsigned int> cnt((size_t)nmaps, 0u);
-    bool any = false;
-    for (int m = 0; m < nmaps; ++m) any = any || centres[2 * m] >= 0;
-    if (any) HIPCHK(hipMemcpyAsync(cnt.data(), d_reveal_cnt, sizeof(unsigned int) * nmaps, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    reveal_busy = false;
-    for (int m = 0; m < nmaps; ++m) changed[m] = centres[2 * m] >= 0 ? cnt[m] : 0u;
-    return UFM_OK;
-}
-
-// ---- cost layers: the caller's raster == max over the layers, kept at a cost proportional to the patch ----
-// profiling: the events the next layer kernel's dispatch carries (null while profiling is off)
-int Engine::layer_events(hipEvent_t *e0, hipEvent_t *e1) {
-    *e0 = *e1 = nullptr;
-    lay_timed = false;
-    if (!profiling) return UFM_OK;
-    for (auto &e : lay_ev) if (!e) HIPCHK(hipEventCreate(&e));
-    *e0 = lay_ev[0]; *e1 = lay_ev[1];
-    lay_timed = true;
-    return UFM_OK;
-}
-// The buffers a composed patch of n cells needs on its way through patch_raw() / patch(): as there, whatever can fail -- applying what is
-// held, the growth of the buffers -- comes before the first write to any store.
-static int layers_make_room(Engine *e, int m, int x, int y, int w, int h) {
-    { int rc = e->flush_deferred(); if (rc != UFM_OK) return rc; }
-    size_t largest = (size_t)w * h;
-    if (e->cs.on) {
-        const PatchRect g = grow_rect(PatchRect{m, x, y, w, h}, e->cs.mh, e->cs.mw, e->cs.ar, e->cs.ac, e->L, e->W);
-        largest = (size_t)g.w * g.h;
-        if (largest > e->d_cs_patch_cap) {
-            const size_t cap = std::max<size_t>(largest, 4096);
-            { int rc = regrow(e->stream, cap, e->d_cs_patch_cap, cap, e->d_cs_patch); if (rc != UFM_OK) return rc; }
-        }
-    }
-    return e->ensure_pmask(largest);
-}
-// ufm_patch_layer*, stream-ordered: the bytes into layer k, the maximum over the layers of that rectangle into the dense scratch patch,
-// that one through the route the caller's device patch takes.  The whole map (ufm_set_layer): a copy and the vector kernel.
-int Engine::patch_layer(int m, int k, const uint8_t *dev_patch, int x, int y, int w, int h) {
-    if (m < 0 || m >= nmaps || !allocated || !maps[m].have_map || !layers_index_ok(k, n_layers)) return UFM_ERR_INVALID;
-    if (!layers_rect_ok(x, y, w, h, L, W)) return UFM_ERR_INVALID;            // Graph.cpp:38-41
-    const size_t n = (size_t)w * h;
-    if (n > d_lcomp_cap) {
-        const size_t cap = std::max<size_t>(n, 4096);
-        { int rc = regrow(stream, cap, d_lcomp_cap, cap, d_lcomp); if (rc != UFM_OK) return rc; }
-    }
-    { int rc = layers_make_room(this, m, x, y, w, h); if (rc != UFM_OK) return rc; }
-    hipEvent_t e0, e1;
-    { int rc = layer_events(&e0, &e1); if (rc != UFM_OK) return rc; }
-    if (layers_rect_is_map(x, y, w, h, L, W)) {
-        HIPCHK(hipMemcpyAsync(layer_ptr(k, m), dev_patch, n, hipMemcpyDeviceToDevice, stream));
-        LayerComposeAllJob j{};
-        for (int l = 0; l < n_layers; ++l) j.layer[l] = layer_ptr(l, m);
-        j.out = d_lcomp; j.cells = n; j.n = n_layers;
-        const LayersSplit s = layers_split(reinterpret_cast<uintptr_t>(j.out), n);
-        launch(k_layer_compose_all, dim3(layers_all_grid(s.nvec)), dim3(LAYERS_THREADS), stream, e0, e1, j);
-    } else {
-        LayerComposeJob j{};
-        for (int l = 0; l < n_layers; ++l) j.layer[l] = layer_ptr(l, m);
-        j.patch = dev_patch; j.out = d_lcomp;
-        j.n = n_layers; j.k = k; j.W = W; j.x = x; j.y = y; j.w = w; j.h = h;
-        launch(k_layer_compose, dim3(layers_rect_grid(w * h)), dim3(LAYERS_THREADS), stream, e0, e1, j);
-    }
-    HIPCHK(hipGetLastError());
-    return cs.on ? patch_raw(m, d_lcomp, x, y, w, h) : patch(m, d_lcomp, x, y, w, h, false);
-}
-// ufm_reveal* with n > 1: one k_reveal_layers for all layers of all maps, then every map's slot through the route its device patch takes
-// (patch() declines the deferral while there are layers)
-int Engine::reveal_layers(const int32_t *centres) {
-    { int rc = reveal_check(centres); if (rc != UFM_OK) return rc; }
-    bool any = false;
-    for (int m = 0; m < nmaps; ++m) any = any || centres[2 * m] >= 0;
-    if (!any) return UFM_OK;
-    { int rc = flush_deferred(); if (rc != UFM_OK) return rc; }
-    const size_t stride = sensor_slot_stride(sensor.mw, sensor.mh), need = stride * (size_t)nmaps;
-    if (need > d_reveal_cap) { int rc = regrow(stream, need, d_reveal_cap, need, d_reveal); if (rc != UFM_OK) return rc; }
-    size_t largest = (size_t)sensor.mw * sensor.mh;
-    if (cs.on) {
-        largest = (size_t)(sensor.mw + cs.mw - 1) * (size_t)(sensor.mh + cs.mh - 1);
-        if (largest > d_cs_patch_cap) {
-            const size_t cap = std::max<size_t>(largest, 4096);
-            { int rc = regrow(stream, cap, d_cs_patch_cap, cap, d_cs_patch); if (rc != UFM_OK) return rc; }
-        }
-    }
-    { int rc = ensure_pmask(largest); if (rc != UFM_OK) return rc; }
-    if (!h_lcentres) HIPCHK(hipHostMalloc(&h_lcentres, sizeof(int32_t) * 3 * (size_t)nmaps, hipHostMallocMapped));
-    if (reveal_busy) { HIPCHK(hipStreamSynchronize(stream)); reveal_busy = false; }
-    for (int m = 0; m < nmaps; ++m) {
-        h_lcentres[3 * m] = centres[2 * m]; h_lcentres[3 * m + 1] = centres[2 * m + 1];
-        h_lcentres[3 * m + 2] = layer_surveys(m);
-    }
-    __atomic_thread_fence(__ATOMIC_RELEASE);
-    HIPCHK(hipMemsetAsync(d_reveal_cnt, 0, sizeof(unsigned int) * nmaps, stream));
-    RevealLayersJob j{};
-    j.mask = d_sensor; j.layers = d_layers; j.cur = cs.on ? d_raw : P.cost; j.slots = d_reveal; j.count = d_reveal_cnt; j.centres = h_lcentres;
-    j.survey[0] = d_survey;
-    for (int k = 1; k < n_layers; ++k) j.survey[k] = d_lsurvey[k];
-    j.cstride = P.cstride; j.lstride = lstride; j.slot_stride = stride;
-    j.n = n_layers; j.nmaps = nmaps; j.L = L; j.W = W; j.mh = sensor.mh; j.mw = sensor.mw; j.ar = sensor.ar; j.ac = sensor.ac;
-    hipEvent_t e0, e1;
-    { int rc = layer_events(&e0, &e1); if (rc != UFM_OK) return rc; }
-    launch(k_reveal_layers, dim3(sensor_grid_x(sensor.mw, sensor.mh), nmaps), dim3(SENSOR_THREADS), stream, e0, e1, j);
-    HIPCHK(hipGetLastError());
-    reveal_busy = true;
-    for (int m = 0; m < nmaps; ++m) {
-        if (centres[2 * m] < 0) continue;
-        const SensorRect r = sensor_place(centres[2 * m], centres[2 * m + 1], sensor.mh, sensor.mw, sensor.ar, sensor.ac, L, W);
-        const uint8_t *slot = d_reveal + stride * (size_t)m;
-        const int rc = cs.on ? patch_raw(m, slot, r.x, r.y, r.w, r.h) : patch(m, slot, r.x, r.y, r.w, r.h, true);
-        if (rc != UFM_OK) return rc;
-    }
-    return UFM_OK;
 }
 
 // ---- a step: ReplannerBase::step (ReplannerBase.h:43-75) --------------------------------------------------------------------
@@ -1582,302 +1267,16 @@ int engine_destroy(Engine *e) {
     for (hipEvent_t v : e->trk_ev) if (v) hipEventDestroy(v);
     for (hipEvent_t v : e->prep_ev) if (v) hipEventDestroy(v);
     e->census_free();
-    free_all(hipFree, e->d_sensor, e->d_reveal, e->d_reveal_cnt, e->d_image);
+    free_all(hipFree, e->d_sensor, e->d_reveal_cnt);
     free_all(hipHostFree, e->h_centres);
     for (hipEvent_t v : e->lay_ev) if (v) hipEventDestroy(v);
-    free_all(hipFree, e->d_lcomp);
-    free_all(hipHostFree, e->h_lcentres);
-    free_all(hipFree, e->d_cs_patch, e->d_patch, e->d_pmask, e->d_field, e->d_info, e->d_jobs, e->d_path);
-    free_all(hipHostFree, e->h_jobs, e->h_path, e->h_patch, e->h_lazy);
+    for (GrowBuf *b : {&e->d_patch, &e->d_pmask, &e->d_cs_patch, &e->d_reveal, &e->d_image, &e->d_lcomp}) b->release();
+    free_all(hipFree, e->d_field, e->d_info, e->d_jobs, e->d_path);
+    free_all(hipHostFree, e->h_jobs, e->h_path, e->h_lazy);
     e->drop_graphs();
     free_all(hipHostFree, e->h_ctr, e->h_pipe_ctr[0], e->h_pipe_ctr[1], e->h_job, e->scratch.acc, e->h_bnd);
     if (e->stream) hipStreamDestroy(e->stream);
     delete e;
-    return UFM_OK;
-}
-
-// What ufm_set_map* and ufm_set_image* share: map m gets a new raster of width x length.  fill(dst) queues whatever writes the caller's
-// raster to dst -- map m's slot of the raw store with a footprint, of the planning raster without -- and does everything of its own that
-// can fail before its first write; the rest is the same for both: held patches first, (re)allocation under the batch's one-size rule,
-// the dilation, the census, the cost windows, the mean traversable cost, an empty step-delta baseline, the goal's validity.
-template <class Fill> int engine_new_raster(Engine *e, int m, int width, int length, Fill &&fill) {
-    HIPCHK(hipSetDevice(e->device));
-    if (e->allocated) { int rc = e->flush_deferred(); if (rc != UFM_OK) return rc; }   // (patches held back belong before the new raster)
-    if (!e->allocated || width != e->W || length != e->L) {
-        bool others = false;
-        for (int k = 0; k < e->nmaps; ++k) if (k != m && e->maps[k].have_map) others = true;
-        if (e->allocated && others) return UFM_ERR_INVALID;   // all maps of a batch share one size
-        int rc = e->alloc(width, length);
-        if (rc != UFM_OK) return rc;
-        if (e->census_on) HIPCHK(hipMemsetAsync(e->d_census, 0, sizeof(uint32_t) * CENSUS_BINS * e->nmaps, e->stream));   // (no map has a raster)
-    }
-    // (a footprint: the input is the raw raster -- kept, and dilated into the planning raster before anything reads that one)
-    { int rc = fill((e->cs.on ? e->d_raw : e->P.cost) + (size_t)m * e->P.cstride); if (rc != UFM_OK) return rc; }
-    if (e->n_layers > 1) {   // (layers: the argument is layer 0, the others start at zero -- rock_aboundance_l = np.zeros(...), run_test.py:102)
-        HIPCHK(hipMemcpyAsync(e->layer_ptr(0, m), (e->cs.on ? e->d_raw : e->P.cost) + (size_t)m * e->P.cstride, e->P.cstride, hipMemcpyDeviceToDevice, e->stream));
-        for (int k = 1; k < e->n_layers; ++k) HIPCHK(hipMemsetAsync(e->layer_ptr(k, m), 0, e->P.cstride, e->stream));
-    }
-    if (e->cs.on) e->cspace_dilate(m, e->P.cost + (size_t)m * e->P.cstride, width, PatchRect{m, 0, 0, width, length});
-    if (e->census_on) { e->census_build(m); e->census_publish(); }      // (the planning raster is final; published by the wait below)
-    k_cost_windows<<<2048, 256, 0, e->stream>>>(e->P, m);
-    {   // mean traversable cost -> default ordering band
-        unsigned long long *d_acc = reinterpret_cast<unsigned long long *>(e->d_scratch);
-        HIPCHK(hipMemsetAsync(d_acc, 0, 2 * sizeof(unsigned long long), e->stream));
-        k_cost_stats<<<512, 256, 0, e->stream>>>(e->P.cost + (size_t)m * e->P.cstride, (size_t)width * length, e->thr_uchar, d_acc);
-        unsigned long long *h_acc = e->scratch.acc;
-        HIPCHK(hipMemcpyAsync(h_acc, d_acc, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
-        HIPCHK(hipStreamSynchronize(e->stream));
-        if (h_acc[1] > 0) e->mean_cost = (float)((double)h_acc[0] / (double)h_acc[1]);
-    }
-    if (e->track) { int rc = e->track_reset(m); if (rc != UFM_OK) return rc; }   // a new raster: the caller's view of this map starts empty again
-    e->maps[m].have_map = true;   // initialize_graph = false, ReplannerBase.h:87
-    // goal element validity depends on the map size
-    MapState &ms = e->maps[m];
-    if (ms.goal_set) ms.goal_elem_valid = ms.goal_ex >= 0 && ms.goal_ey >= 0 && ms.goal_ex < e->P.EX && ms.goal_ey < e->P.EY;
-    return UFM_OK;
-}
-
-int engine_set_map(Engine *e, int m, const uint8_t *src, bool on_device, int width, int length) {
-    if (!e || !src || m < 0 || m >= e->nmaps || width <= 0 || length <= 0) return UFM_ERR_INVALID;
-    return engine_new_raster(e, m, width, length, [&](uint8_t *dst) -> int {
-        HIPCHK(hipMemcpyAsync(dst, src, (size_t)width * length, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, e->stream));
-        return UFM_OK;
-    });
-}
-
-// ufm_set_image* / ufm_batch_set_image*: the bitmap becomes map m's raster AND its survey (k_prepare, one launch).  The survey's array and
-// the staging buffer are seen to before k_prepare writes either raster; the wait at the end of engine_new_raster() is what frees the
-// caller's buffer -- and the staging buffer for the next map.
-int engine_set_image(Engine *e, int m, const uint8_t *src, bool on_device, int width, int length, const uint16_t *taps, int ntaps, int penalty) {
-    PrepTaps k;
-    if (!e || !src || m < 0 || m >= e->nmaps || !prep_args_valid(taps, ntaps, width, length, penalty) || !prep_pack(taps, ntaps, &k)) return UFM_ERR_INVALID;
-    if (e->allocated && (width != e->W || length != e->L))       // (the one-size rule of a batch, before anything is flushed or freed)
-        for (int j = 0; j < e->nmaps; ++j) if (j != m && e->maps[j].have_map) return UFM_ERR_INVALID;
-    bool timed = false;
-    const int rc = engine_new_raster(e, m, width, length, [&](uint8_t *dst) -> int {
-        const size_t n = (size_t)width * length, all = e->P.cstride * e->nmaps;
-        if (!e->d_survey) {
-            if (hipMalloc(&e->d_survey, all) != hipSuccess) { (void)hipGetLastError(); e->d_survey = nullptr; return UFM_ERR_NOMEM; }
-            e->have_survey.assign((size_t)e->nmaps, 0);
-        }
-        const uint8_t *image = src;
-        if (!on_device || prep_overlap(src, n, e->P.cost, all) || prep_overlap(src, n, e->d_survey, all) || (e->cs.on && prep_overlap(src, n, e->d_raw, all))) {
-            if (n > e->d_image_cap) { int rc2 = regrow(e->stream, n, e->d_image_cap, n, e->d_image); if (rc2 != UFM_OK) return rc2; }
-            HIPCHK(hipMemcpyAsync(e->d_image, src, n, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, e->stream));
-            image = e->d_image;
-        }
-        PrepareJob j{};
-        j.src = image; j.out_l = dst; j.out_h = e->d_survey + (size_t)m * e->P.cstride;
-        j.W = width; j.L = length; j.penalty = penalty;
-        j.wide_in = width % 4 == 0 && prep_aligned4(j.src);
-        j.wide_out = width % 4 == 0 && prep_aligned4(j.out_l) && prep_aligned4(j.out_h);
-        j.taps = k;
-        timed = e->profiling;
-        if (timed && !e->prep_ev[0]) { HIPCHK(hipEventCreate(&e->prep_ev[0])); HIPCHK(hipEventCreate(&e->prep_ev[1])); }
-        launch(k_prepare, dim3(prep_grid_x(width), prep_grid_y(length)), dim3(PREP_THREADS), e->stream, timed ? e->prep_ev[0] : nullptr,
-               timed ? e->prep_ev[1] : nullptr, j);
-        HIPCHK(hipGetLastError());
-        e->have_survey[m] = 1;
-        return UFM_OK;
-    });
-    if (rc != UFM_OK) return rc;
-    e->reveal_busy = false;                  // (the call has waited for the stream)
-    if (timed) HIPCHK(hipEventElapsedTime(&e->prep_ms, e->prep_ev[0], e->prep_ev[1]));
-    return UFM_OK;
-}
-
-// ufm_patch_layer* / ufm_batch_patch_layer*, and ufm_patch_map* while there are layers (k = 0): checked whole before the staging copy
-int engine_patch_layer(Engine *e, int m, int k, const uint8_t *src, bool on_device, int x, int y, int w, int h) {
-    if (!e || !src || m < 0 || m >= e->nmaps || !e->allocated || !e->maps[m].have_map) return UFM_ERR_INVALID;
-    if (!layers_index_ok(k, e->n_layers) || !layers_rect_ok(x, y, w, h, e->L, e->W)) return UFM_ERR_INVALID;
-    HIPCHK(hipSetDevice(e->device));
-    if (on_device) return e->patch_layer(m, k, src, x, y, w, h);
-    const size_t n = (size_t)w * h;
-    if (n > e->d_patch_cap) {
-        const size_t cap = n < 4096 ? 4096 : n;
-        { int rc = regrow(e->stream, cap, e->d_patch_cap, cap, e->d_patch, &e->h_patch); if (rc != UFM_OK) return rc; }
-    } else {
-        HIPCHK(hipStreamSynchronize(e->stream));   // staging buffers are reused
-    }
-    std::memcpy(e->h_patch, src, n);
-    HIPCHK(hipMemcpyAsync(e->d_patch, e->h_patch, n, hipMemcpyHostToDevice, e->stream));
-    return e->patch_layer(m, k, e->d_patch, x, y, w, h);
-}
-// ufm_set_layer*: layer k wholesale, a whole-map patch -- not a set_map: the field is kept and the next step replans
-int engine_set_layer(Engine *e, int m, int k, const uint8_t *src, bool on_device, int width, int length) {
-    if (!e || !e->allocated || width != e->W || length != e->L) return UFM_ERR_INVALID;
-    return engine_patch_layer(e, m, k, src, on_device, 0, 0, width, length);
-}
-// ufm_set_layers / ufm_batch_set_layers: a property of the handle, set before the first raster
-int engine_set_layers(Engine *e, int n) {
-    if (!e || !layers_count_ok(n)) return UFM_ERR_INVALID;
-    for (const MapState &ms : e->maps) if (ms.have_map) return UFM_ERR_INVALID;
-    // (arrays without a map -- a ufm_set_map that failed after its allocation -- were sized for the old count: the next one allocates anew)
-    if (e->allocated) { HIPCHK(hipSetDevice(e->device)); e->release(); }
-    e->n_layers = n;
-    return UFM_OK;
-}
-int engine_read_layer(Engine *e, int m, int k, uint8_t *out) {
-    if (!e || !out || m < 0 || m >= e->nmaps || !e->allocated || !e->maps[m].have_map || !layers_index_ok(k, e->n_layers)) return UFM_ERR_INVALID;
-    HIPCHK(hipSetDevice(e->device));
-    HIPCHK(hipMemcpyAsync(out, e->layer_ptr(k, m), e->P.cstride, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return UFM_OK;
-}
-
-int engine_patch(Engine *e, int m, const uint8_t *src, bool on_device, int x, int y, int w, int h) {
-    if (!e || !src) return UFM_ERR_INVALID;
-    if (e->n_layers > 1) return engine_patch_layer(e, m, 0, src, on_device, x, y, w, h);
-    HIPCHK(hipSetDevice(e->device));
-    if (on_device) return e->cs.on ? e->patch_raw(m, src, x, y, w, h) : e->patch(m, src, x, y, w, h, true);
-    if (w <= 0 || h <= 0) return UFM_ERR_INVALID;
-    {   // a small patch of a single planner: held in pinned memory for the replan's block kernel (Engine::patch_lazy)
-        bool taken = false;
-        const int rc = e->patch_lazy(m, src, x, y, w, h, &taken);
-        if (rc != UFM_OK || taken) return rc;
-    }
-    const size_t n = (size_t)w * h;
-    if (n > e->d_patch_cap) {
-        const size_t cap = n < 4096 ? 4096 : n;
-        { int rc = regrow(e->stream, cap, e->d_patch_cap, cap, e->d_patch, &e->h_patch); if (rc != UFM_OK) return rc; }
-    } else {
-        HIPCHK(hipStreamSynchronize(e->stream));   // staging buffers are reused
-    }
-    std::memcpy(e->h_patch, src, n);
-    HIPCHK(hipMemcpyAsync(e->d_patch, e->h_patch, n, hipMemcpyHostToDevice, e->stream));
-    return e->cs.on ? e->patch_raw(m, e->d_patch, x, y, w, h) : e->patch(m, e->d_patch, x, y, w, h);
-}
-
-// ufm_set_cspace / ufm_batch_set_cspace: a property of the vehicle, set before the first raster
-int engine_set_cspace(Engine *e, const uint8_t *mask, int mw, int mh, int ar, int ac) {
-    if (!e) return UFM_ERR_INVALID;
-    for (const MapState &ms : e->maps) if (ms.have_map) return UFM_ERR_INVALID;
-    if (!cspace_pack(mask, mw, mh, ar, ac, &e->cs)) return UFM_ERR_INVALID;
-    // (arrays without a map -- a ufm_set_map that failed after its allocation -- were sized without the raw store: the next one allocates anew)
-    if (e->allocated) { HIPCHK(hipSetDevice(e->device)); e->release(); }
-    return UFM_OK;
-}
-int engine_read_raw_map(Engine *e, int m, uint8_t *host_map) {
-    if (!e || !host_map || !e->cs.on || !e->allocated || m < 0 || m >= e->nmaps || !e->maps[m].have_map) return UFM_ERR_INVALID;
-    HIPCHK(hipSetDevice(e->device));
-    HIPCHK(hipMemcpyAsync(host_map, e->d_raw + (size_t)m * e->P.cstride, e->P.cstride, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return UFM_OK;
-}
-
-// ufm_set_sensor / ufm_batch_set_sensor: the field of view, set or replaced between any two calls; needs no map
-int engine_set_sensor(Engine *e, const uint8_t *mask, int mw, int mh, int ar, int ac) {
-    if (!e) return UFM_ERR_INVALID;
-    SensorShape s;
-    if (!sensor_pack(mask, mw, mh, ar, ac, &s)) return UFM_ERR_INVALID;
-    HIPCHK(hipSetDevice(e->device));
-    if (!e->d_sensor) {
-        const int rc = [&]() -> int {
-            HIPCHK(hipMalloc(&e->d_sensor, (size_t)SENSOR_MAX * SENSOR_MAX));
-            HIPCHK(hipMalloc(&e->d_reveal_cnt, sizeof(unsigned int) * e->nmaps));
-            HIPCHK(hipHostMalloc(&e->h_centres, sizeof(int32_t) * 2 * e->nmaps, hipHostMallocMapped));
-            return UFM_OK;
-        }();
-        if (rc != UFM_OK) {
-            free_all(hipFree, e->d_sensor, e->d_reveal_cnt); free_all(hipHostFree, e->h_centres);
-            e->d_sensor = nullptr; e->d_reveal_cnt = nullptr; e->h_centres = nullptr;
-            return rc;
-        }
-        e->have_survey.resize((size_t)e->nmaps, 0);
-    }
-    // (a reveal that is only queued reads the old mask: wait for it, then replace the bytes)
-    HIPCHK(hipStreamSynchronize(e->stream));
-    e->reveal_busy = false;
-    HIPCHK(hipMemcpy(e->d_sensor, mask, (size_t)mw * mh, hipMemcpyHostToDevice));
-    e->sensor = s;
-    return UFM_OK;
-}
-// ufm_set_survey* / ufm_batch_set_survey*: what the sensor would see of map m, for the raster that map has
-int engine_set_survey(Engine *e, int m, const uint8_t *src, bool on_device, int width, int length) {
-    if (!e || !src || m < 0 || m >= e->nmaps || !e->allocated || !e->maps[m].have_map || width != e->W || length != e->L) return UFM_ERR_INVALID;
-    HIPCHK(hipSetDevice(e->device));
-    if (!e->d_survey) {
-        if (hipMalloc(&e->d_survey, e->P.cstride * e->nmaps) != hipSuccess) { (void)hipGetLastError(); e->d_survey = nullptr; return UFM_ERR_NOMEM; }
-        e->have_survey.assign((size_t)e->nmaps, 0);
-    }
-    HIPCHK(hipMemcpyAsync(e->d_survey + (size_t)m * e->P.cstride, src, e->P.cstride, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));      // (the caller's buffer is free again when the call returns)
-    e->reveal_busy = false;
-    e->have_survey[m] = 1;
-    return UFM_OK;
-}
-int engine_read_survey(Engine *e, int m, uint8_t *host_survey) {
-    if (!e || !host_survey || m < 0 || m >= e->nmaps || !e->allocated || !e->d_survey || !e->have_survey[m]) return UFM_ERR_INVALID;
-    HIPCHK(hipSetDevice(e->device));
-    HIPCHK(hipMemcpyAsync(host_survey, e->d_survey + (size_t)m * e->P.cstride, e->P.cstride, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return UFM_OK;
-}
-
-// ufm_set_layer_survey* / ufm_batch_set_layer_survey*: what the sensor would see of layer k of map m; k = 0 is ufm_set_survey
-int engine_set_layer_survey(Engine *e, int m, int k, const uint8_t *src, bool on_device, int width, int length) {
-    if (k == 0) return engine_set_survey(e, m, src, on_device, width, length);
-    if (!e || !src || m < 0 || m >= e->nmaps || !e->allocated || !e->maps[m].have_map || width != e->W || length != e->L) return UFM_ERR_INVALID;
-    if (!layers_index_ok(k, e->n_layers)) return UFM_ERR_INVALID;
-    HIPCHK(hipSetDevice(e->device));
-    if (!e->d_lsurvey[k]) {
-        if (hipMalloc(&e->d_lsurvey[k], e->P.cstride * e->nmaps) != hipSuccess) { (void)hipGetLastError(); e->d_lsurvey[k] = nullptr; return UFM_ERR_NOMEM; }
-        e->have_lsurvey[k].assign((size_t)e->nmaps, 0);
-    }
-    HIPCHK(hipMemcpyAsync(e->d_lsurvey[k] + (size_t)m * e->P.cstride, src, e->P.cstride, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));      // (the caller's buffer is free again when the call returns)
-    e->reveal_busy = false;
-    e->have_lsurvey[k][m] = 1;
-    return UFM_OK;
-}
-int engine_read_layer_survey(Engine *e, int m, int k, uint8_t *host_survey) {
-    if (!e || !host_survey || m < 0 || m >= e->nmaps || !e->allocated || !layers_index_ok(k, e->n_layers) || !((e->layer_surveys(m) >> k) & 1)) return UFM_ERR_INVALID;
-    HIPCHK(hipSetDevice(e->device));
-    const uint8_t *src = (k == 0 ? e->d_survey : e->d_lsurvey[k]) + (size_t)m * e->P.cstride;
-    HIPCHK(hipMemcpyAsync(host_survey, src, e->P.cstride, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
-    return UFM_OK;
-}
-
-// ufm_track_costs / ufm_batch_track_costs.  On, with maps already set: what is held is applied and the counters are built from the rasters
-// as they stand.  Off frees everything; refused while "auto_multiplier" is 1 (the step would have nothing to take).
-int engine_track_costs(Engine *e, int enable) {
-    if (!e) return UFM_ERR_INVALID;
-    HIPCHK(hipSetDevice(e->device));
-    if (!enable) {
-        if (!e->census_on) return UFM_OK;
-        if (e->auto_multiplier) return UFM_ERR_INVALID;
-        HIPCHK(hipStreamSynchronize(e->stream));
-        e->census_free();
-        return UFM_OK;
-    }
-    if (e->census_on) return UFM_OK;
-    if (e->allocated) { int rc = e->flush_deferred(); if (rc != UFM_OK) return rc; }
-    const int rc = [&]() -> int {
-        HIPCHK(hipMalloc(&e->d_census, sizeof(uint32_t) * CENSUS_BINS * e->nmaps));
-        void *pub = nullptr;
-        HIPCHK(hipHostMalloc(&pub, 128, hipHostMallocMapped | hipHostMallocCoherent));
-        std::memset(pub, 0, 128);
-        e->h_cen = static_cast<int *>(pub);
-        e->h_cen_flag = reinterpret_cast<unsigned int *>(static_cast<char *>(pub) + 64);
-        e->cen_seq = 0;
-        HIPCHK(hipMemsetAsync(e->d_census, 0, sizeof(uint32_t) * CENSUS_BINS * e->nmaps, e->stream));
-        for (int m = 0; m < e->nmaps; ++m) if (e->allocated && e->maps[m].have_map) e->census_build(m);
-        e->census_publish();
-        HIPCHK(hipGetLastError());
-        return UFM_OK;
-    }();
-    if (rc != UFM_OK) { (void)hipStreamSynchronize(e->stream); e->census_free(); return rc; }
-    e->census_on = true;
-    return UFM_OK;
-}
-// the counters of map m, as they are once everything queued has run
-int engine_read_census(Engine *e, int m, uint32_t out[CENSUS_BINS]) {
-    if (!e || !e->census_on || !e->allocated || m < 0 || m >= e->nmaps || !e->maps[m].have_map) return UFM_ERR_INVALID;
-    HIPCHK(hipSetDevice(e->device));
-    { int rc = e->flush_deferred(); if (rc != UFM_OK) return rc; }
-    HIPCHK(hipMemcpyAsync(out, e->d_census + (size_t)m * CENSUS_BINS, sizeof(uint32_t) * CENSUS_BINS, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipStreamSynchronize(e->stream));
     return UFM_OK;
 }
 
