@@ -88,13 +88,6 @@ __global__ void k_delta_commit(DeltaRecords o, unsigned int n, int TY, float *ba
 }
 
 // ---- host side ----
-void Engine::track_free() {
-    if (stream && (trk_g || trk_key || trk_rec)) hipStreamSynchronize(stream);
-    if (trk_g) hipFree(trk_g);
-    if (trk_key) hipFree(trk_key);
-    if (trk_rec) hipFree(trk_rec);
-    trk_g = nullptr; trk_key = nullptr; trk_rec = nullptr; trk_cap = 0;
-}
 // the empty ExpandedMap: every element +inf, no Info (map m, or all maps with m < 0)
 int Engine::track_reset(int m) {
     const size_t first = m < 0 ? 0 : (size_t)m * P.gstride, n = m < 0 ? P.gstride * nmaps : P.gstride;
@@ -105,17 +98,10 @@ int Engine::track_reset(int m) {
 }
 int Engine::track_alloc() {              // (the field is allocated)
     track_free();
-    if (hipMalloc(&trk_g, P.gstride * nmaps * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); trk_g = nullptr; return UFM_ERR_NOMEM; }
-    if (opt_lvl >= 1 && hipMalloc(&trk_key, P.gstride * nmaps) != hipSuccess) { (void)hipGetLastError(); trk_key = nullptr; track_free(); return UFM_ERR_NOMEM; }
+    int rc = trk_g.alloc(P.gstride * nmaps);
+    if (rc == UFM_OK && opt_lvl >= 1) rc = trk_key.alloc(P.gstride * nmaps);
+    if (rc != UFM_OK) { track_free(); return rc; }
     return track_reset(-1);
-}
-int Engine::track_records(size_t cap) {  // the record buffer, at least `cap` records
-    if (cap <= trk_cap) return UFM_OK;
-    if (trk_rec) { HIPCHK(hipStreamSynchronize(stream)); hipFree(trk_rec); trk_rec = nullptr; trk_cap = 0; }
-    cap = (cap + 63) / 64 * 64;
-    if (hipMalloc(&trk_rec, 256 + cap * 21) != hipSuccess) { (void)hipGetLastError(); trk_rec = nullptr; return UFM_ERR_NOMEM; }
-    trk_cap = cap;
-    return UFM_OK;
 }
 
 int engine_track_changes(Engine *e, int enable) {
@@ -140,18 +126,19 @@ int engine_read_changes(Engine *e, int m, int cap, int32_t *xy, float *g, int32_
     uint8_t *base_key = has_info ? e->trk_key + (size_t)m * e->P.gstride : nullptr;
     const int nchunks = (int)(e->P.gstride / DELTA_CHUNK);
     const int grid = std::min((nchunks + 3) / 4, 256 * 8);       // 8 workgroups of 4 waves per CU keep the loads in flight
-    if (e->profiling && !e->trk_ev[0]) { HIPCHK(hipEventCreate(&e->trk_ev[0])); HIPCHK(hipEventCreate(&e->trk_ev[1])); }
+    if (e->profiling) { int rc = e->trk_ev.ensure(); if (rc != UFM_OK) return rc; }
     { int rc = e->track_records(65536); if (rc != UFM_OK) return rc; }   // (a replan's delta is a few thousand records; it grows below when one is larger)
     unsigned int cnt = 0;
     DeltaRecords o{};
     for (int pass = 0; pass < 2; ++pass) {
-        char *q = static_cast<char *>(e->trk_rec);
+        uint8_t *q = e->trk_rec;
+        const size_t rec_cap = e->trk_cap();
         o.count = reinterpret_cast<unsigned int *>(q);
         o.xy = reinterpret_cast<int32_t *>(q + 256);
-        o.g = reinterpret_cast<float *>(q + 256 + e->trk_cap * 8);
-        o.info = reinterpret_cast<int32_t *>(q + 256 + e->trk_cap * 12);
-        o.key = reinterpret_cast<uint8_t *>(q + 256 + e->trk_cap * 20);
-        o.cap = (unsigned int)e->trk_cap;
+        o.g = reinterpret_cast<float *>(q + 256 + rec_cap * 8);
+        o.info = reinterpret_cast<int32_t *>(q + 256 + rec_cap * 12);
+        o.key = q + 256 + rec_cap * 20;
+        o.cap = (unsigned int)rec_cap;
         HIPCHK(hipMemsetAsync(o.count, 0, sizeof(unsigned int), e->stream));
         if (e->profiling) HIPCHK(hipEventRecord(e->trk_ev[0], e->stream));
         if (has_info) k_delta_scan<true><<<grid, DELTA_WG, 0, e->stream>>>(F, bp, base_g, base_key, nchunks, o);

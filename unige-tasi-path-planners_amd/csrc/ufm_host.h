@@ -43,37 +43,43 @@ void launch(void (*k)(KA...), dim3 g, dim3 b, hipStream_t s, hipEvent_t e0, hipE
     else k<<<g, b, 0, s>>>(static_cast<KA>(a)...);
 }
 
-// A grow-on-demand device buffer of capacity `cap`, with a pinned twin if `pinned` is given: wait for the stream if there is something to
-// free (always_sync: in any case), free, allocate `bytes` anew; the capacity is 0 until that has succeeded, `new_cap` then.
-template <class P> int regrow(hipStream_t s, size_t bytes, size_t &cap, size_t new_cap, P *&dev, P **pinned = nullptr, bool always_sync = false) {
-    cap = 0;
-    if (always_sync || dev || (pinned && *pinned)) HIPCHK(hipStreamSynchronize(s));
-    if (dev) hipFree(dev);
-    if (pinned && *pinned) hipHostFree(*pinned);
-    dev = nullptr;                       // nothing dangling if an allocation below fails
-    if (pinned) *pinned = nullptr;
-    HIPCHK(hipMalloc(&dev, bytes));
-    if (pinned) HIPCHK(hipHostMalloc(pinned, bytes));
-    cap = new_cap;
-    return UFM_OK;
+// ---- what the engine owns (ufm_resources.h), over HIP.  One error mapping for every allocation, event and wait of the owners: out of
+// memory is UFM_ERR_NOMEM, anything else UFM_ERR_HIP_BASE - e, and the runtime's sticky error is cleared either way.
+using ResStream = hipStream_t;
+using ResEvent = hipEvent_t;
+#include "ufm_resources.h"
+static_assert(UFM_OK == 0, "the owners report success as 0");
+int res_code(hipError_t e) {
+    if (e == hipSuccess) return UFM_OK;
+    (void)hipGetLastError();
+    return e == hipErrorOutOfMemory ? UFM_ERR_NOMEM : UFM_ERR_HIP_BASE - (int)e;
 }
-
-template <class... Q> void free_all(hipError_t (*release)(void *), Q *...q) { ((q ? (void)release(q) : (void)0), ...); }
-
-// A grow-only scratch buffer of bytes (regrow above): reserve() leaves at least `bytes` of capacity, never fewer than 4096 once there is any;
-// `twin`: with a pinned buffer of the same size.  A buffer that grows is a new one: what was queued on the old one has been waited for.
-struct GrowBuf {
-    uint8_t *dev = nullptr, *pinned = nullptr;
-    size_t cap = 0;
-    int reserve(hipStream_t s, size_t bytes, bool twin = false) {
-        if (bytes <= cap) return UFM_OK;
-        const size_t n = std::max<size_t>(bytes, 4096);
-        return regrow(s, n, cap, n, dev, twin ? &pinned : nullptr);
-    }
-    void release() { free_all(hipFree, dev); free_all(hipHostFree, pinned); dev = pinned = nullptr; cap = 0; }
+int res_dev_alloc(void **p, size_t bytes) { *p = nullptr; return res_code(hipMalloc(p, bytes ? bytes : 1)); }
+void res_dev_free(void *p) { (void)hipFree(p); }
+int res_pin_alloc(void **p, size_t bytes, Pin kind) {
+    *p = nullptr;
+    return res_code(hipHostMalloc(p, bytes, kind == Pin::Default ? hipHostMallocDefault : kind == Pin::Mapped ? hipHostMallocMapped : hipHostMallocMapped | hipHostMallocCoherent));
+}
+void res_pin_free(void *p) { (void)hipHostFree(p); }
+int res_event_create(hipEvent_t *e) { *e = nullptr; return res_code(hipEventCreate(e)); }
+void res_event_destroy(hipEvent_t e) { (void)hipEventDestroy(e); }
+int res_stream_sync(hipStream_t s) { return res_code(hipStreamSynchronize(s)); }
+using ScratchBytes = GrowArray<uint8_t, 4096>;   // the map side's scratch: bytes, never fewer than 4096 once there are any
+struct StreamOwner {                             // the engine's stream: its first member, so the last thing it gives back
+    hipStream_t s = nullptr;
+    StreamOwner() = default;
+    StreamOwner(const StreamOwner &) = delete;
+    ~StreamOwner() { if (s) (void)hipStreamDestroy(s); }
+    operator hipStream_t() const { return s; }
 };
 
 struct Engine {
+    StreamOwner stream;              // declared first, destroyed last: behind every buffer and event below
+    ~Engine() {                      // the members give back what they own, in reverse order; first nothing may be running or hold their pointers
+        hipSetDevice(device);
+        if (stream) hipStreamSynchronize(stream);
+        drop_graphs();
+    }
     int algo = 0, opt_lvl = 0, heur = 0, device = 0, nmaps = 1;
     float heuristic_multiplier = 1.0f;
     int thr_uchar = 254;             // Graph.h:34
@@ -81,12 +87,11 @@ struct Engine {
     uint32_t graphs_made = 0;        // replan graphs instantiated so far (ufm_stats::graphs_instantiated)
     int W = 0, L = 0;
     DevParams P{};
+    DevTable bufs;                   // owns what P's pointers and d_scratch point to (buffer_rows(), alloc(), release())
     bool allocated = false;
-    hipStream_t stream = nullptr;
-    DevCounters *h_ctr = nullptr;    // pinned, host-coherent: k_publish writes it, the host spins on h_flag
-    unsigned int *h_flag = nullptr;  // sequence number of the last published copy (same allocation)
-    DevCounters *h_pipe_ctr[2] = {nullptr, nullptr};   // run_phase keeps one batch of launches in flight ahead of the one whose
-    unsigned int *h_pipe_flag[2] = {nullptr, nullptr}; // counters it is looking at: two more published copies, used alternately
+    Published<DevCounters> h_ctr;    // k_publish writes it, the host spins on h_ctr.flag(): the sequence number of the last published copy
+    Published<DevCounters> h_pipe_ctr[2];   // run_phase keeps one batch of launches in flight ahead of the one whose
+                                            // counters it is looking at: two more published copies, used alternately
     bool pipeline_batches = true;
     unsigned int pub_seq = 0;
     bool spin_wait = true;           // false: hipMemcpyAsync + hipStreamSynchronize instead
@@ -97,8 +102,8 @@ struct Engine {
                                      //     ~15 x what a plan of that many tiles takes: a device shared with another long-running kernel)
     float owned_band = -1.0f;        // ... ordering band in tile crossings (< 0: by the job -- 2.5 for a single map of a node planner, 3 for MS-DFM, 2 for a batch: owned_phase())
     uint32_t owned_launches = 0;
-    hipEvent_t own_ev[2] = {nullptr, nullptr};
-    hipEvent_t reg_ev[2] = {nullptr, nullptr};     // profiling: around the block kernel of a replan
+    EventSet<2> own_ev;
+    EventSet<2> reg_ev;              // profiling: around the block kernel of a replan
     bool own_timed = false;
     int owned_flags = 0;             // resident kernel, diagnostics and variants.  1: no tile taken ahead; 2: no early hand-off (FD / SG); 4: early hand-off once per patch and visit;
                                      // 8: early hand-off waits for its stores inside the sweep loop; 16: no in-visit halo refresh; 32: idle workgroups do not help out;
@@ -119,7 +124,7 @@ struct Engine {
                                                  // sending the leftover lowering through the resident kernel instead: 1 111 us)
     int batch_margin = 1;            // replans: launches per phase = most that the last 6 replans needed + this
     float raise_margin = 0.25f;      // invalidation bound = start key + this many ordering bands (a miss costs a second round)
-    ReplanJob *h_job = nullptr;      // host-coherent pinned: per-replan inputs of the graph's first node
+    PinArray<ReplanJob> h_job;       // host-coherent pinned: per-replan inputs of the graph's first node
     struct GraphSig { DevParams P; float band, delta; int max_iters, grid, follow; };
     GraphSig graph_sig{};
     std::vector<std::pair<int, hipGraphExec_t>> graphs;   // key nr * 256 + nl
@@ -133,14 +138,14 @@ struct Engine {
     int replan_graph(int nr, int nl, float band, hipGraphExec_t *out);
     void drop_graphs() { for (auto &g : graphs) hipGraphExecDestroy(g.second); graphs.clear(); }
     struct StepScratch {             // pinned: 2 accumulators + 12 * nmaps ints, one allocation carved once (engine_create)
-        unsigned long long *acc = nullptr;     // [2]: engine_set_map's cost sum and count
+        PinArray<unsigned long long> acc;      // [2]: engine_set_map's cost sum and count; it owns the whole allocation
         int *consume = nullptr, *init = nullptr, *init_tiles = nullptr;   // [nmaps] each: plan_step's answer per map; the goal tiles of the initialising maps, dense
         int *goals = nullptr;                  // [2 * nmaps]
         unsigned int *num_updated = nullptr;   // [nmaps]
         int *start_el = nullptr;               // [4 * nmaps]
         float *start_pos = nullptr;            // [2 * nmaps]
         int carve(int n) {
-            HIPCHK(hipHostMalloc(&acc, 2 * sizeof(unsigned long long) + sizeof(int) * 12 * (size_t)n));
+            { int rc = acc.alloc(2 + 6 * (size_t)n); if (rc != UFM_OK) return rc; }    // (12 ints are 6 of its elements)
             consume = reinterpret_cast<int *>(acc + 2); init = consume + n; init_tiles = init + n; goals = init_tiles + n;
             num_updated = reinterpret_cast<unsigned int *>(goals + 2 * n); start_el = goals + 3 * n;
             start_pos = reinterpret_cast<float *>(start_el + 4 * n);
@@ -148,14 +153,10 @@ struct Engine {
         }
     } scratch;
     int *d_scratch = nullptr;
-    float *d_field = nullptr;        // ufm_read_field: the requested window, dense
-    size_t d_field_cap = 0;
-    int32_t *d_info = nullptr;       // ufm_read_info: back-pointers of the requested window
-    size_t d_info_cap = 0;           // (int32 entries)
-    PathJob *d_jobs = nullptr, *h_jobs = nullptr;     // path extraction: the walks of one launch (h_: pinned)
-    size_t jobs_cap = 0;                              // jobs per buffer
-    float *d_path = nullptr, *h_path = nullptr;       // per-job output records
-    size_t path_cap = 0;                              // floats per buffer
+    GrowArray<float> d_field;        // ufm_read_field: the requested window, dense
+    GrowArray<int32_t> d_info;       // ufm_read_info: back-pointers of the requested window
+    GrowArray<PathJob> d_jobs;       // path extraction: the walks of one launch, with the pinned twin
+    GrowArray<float> d_path;         // ... and the per-job output records, with the pinned twin
     std::vector<MapState> maps;
     std::vector<PatchRect> pending;
     int iter[2] = {0, 0};            // index k of the next relax launch of each queue (never reset: the queues persist)
@@ -163,7 +164,7 @@ struct Engine {
     bool start_cell_floor = false;   // start_cell_ = the cell that contains the start position (floor) instead of Cell(Position)'s roundf (Cell.cpp:20-21): what the
                                      // revision of the reference that wrote its two recorded mission logs did (tests/test_reference_mission.py; oracle: ORC_REV_LOG)
     bool dynamic_mode = true;        // long queues: k_triage + cursor hand-out
-    float *h_bnd = nullptr;          // pinned [nmaps]
+    PinArray<float> h_bnd;           // pinned [nmaps]
     int last_active = 1;             // queue length at the last host check: long queues go through k_triage
     int grid_relax = 512;
     int dyn_grid = 256;              // workgroups of a cursor hand-out launch: the number of CUs
@@ -178,12 +179,13 @@ struct Engine {
     float mean_cost = 1.0f;
     int batch_fixed = 0;
     bool profiling = false;
-    hipEvent_t chain_ev[4] = {nullptr, nullptr, nullptr, nullptr};   // profiling: around the two blind batches of a replan's launch chain
-    std::vector<hipEvent_t> batch_ev;     // ... and the sampled launches of run_phase's batches, batch_ev_slot events per batch in flight
+    EventSet<4> chain_ev;            // profiling: around the two blind batches of a replan's launch chain
+    std::vector<EventSet<1>> batch_ev;    // ... and the sampled launches of run_phase's batches, batch_ev_slot events per batch in flight
     int batch_ev_slot = 64;
-    hipEvent_t *batch_event(int slot, int i) { return &batch_ev[(size_t)slot * batch_ev_slot + i]; }
+    hipEvent_t batch_event(int slot, int i) const { return batch_ev[(size_t)slot * batch_ev_slot + i][0]; }
     ufm_stats last{};
 
+    std::vector<DevRow> buffer_rows();
     int alloc(int width, int length);
     void release();
     void launch_relax(int mode, float rbound, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
@@ -246,8 +248,8 @@ struct Engine {
     int patch_room(const PatchPlan &p);
     int route_patch(PatchSource source, bool host_bytes, int k, const uint8_t *bytes, const PatchRect &r);
     int stage_host_patch(const uint8_t *src, size_t n);
-    GrowBuf d_patch;                 // staging for host patches, with its pinned twin
-    GrowBuf d_pmask;                 // changed-cell mask of the patch being applied
+    ScratchBytes d_patch;            // staging for host patches, with its pinned twin
+    ScratchBytes d_pmask;            // changed-cell mask of the patch being applied
     int ensure_pmask(size_t need);
     void patch_small(int m, const uint8_t *src, int x, int y, int w, int h) {
         with_elements(algo, [&](auto nodes) { k_patch_small<nodes()><<<1, 1024, 0, stream>>>(P, m, src, d_pmask.dev, x, y, w, h); });
@@ -270,7 +272,7 @@ struct Engine {
     static constexpr int LAZY_SLOTS = 4;                  // = the most rectangles a block-kernel job takes
     struct LazyPatch { int m, x, y, w, h, slot; };
     std::vector<LazyPatch> lazy;
-    uint8_t *h_lazy = nullptr;       // LAZY_SLOTS x 4096 bytes, pinned + mapped
+    PinArray<uint8_t> h_lazy;        // LAZY_SLOTS x 4096 bytes, pinned + mapped
     int lazy_next = 0;               // slot after the last one handed out
     bool lazy_dirty[LAZY_SLOTS] = {false, false, false, false};   // a kernel queued on the stream may still read the slot
     bool lazy_patches = true;
@@ -280,37 +282,37 @@ struct Engine {
     // or runs.  On: d_raw holds the caller's raster per map, P.cost its dilation by the footprint; a raw patch goes to d_raw, the rectangle
     // of P.cost it can change is dilated into d_cs_patch and that one is applied as an ordinary patch.
     CspaceMask cs;
-    uint8_t *d_raw = nullptr;        // [nmaps][L][W]
-    GrowBuf d_cs_patch;              // the dilated grown rectangle of the patch being applied, dense
+    DevArray<uint8_t> d_raw;         // [nmaps][L][W]; dropped with the rasters (release())
+    ScratchBytes d_cs_patch;           // the dilated grown rectangle of the patch being applied, dense
     void cspace_dilate(int m, uint8_t *out, int pitch, const PatchRect &r);
     // Cost census (ufm_track_costs; ufm_census.h).  Off -- the default -- nothing below exists or runs.  On: d_census
     // holds, per map, how many cells of P.cost have each value, exactly, between any two calls: built after the raster is final
     // (engine_new_raster), corrected in front of every patch kernel.  After every build or patch the smallest and largest value present
     // are published to h_cen; "auto_multiplier" makes a step take that minimum as its heuristic multiplier.
     bool census_on = false, auto_multiplier = false;
-    uint32_t *d_census = nullptr;    // [nmaps][256]
-    int *h_cen = nullptr;            // pinned, host-coherent: {min, max} over the engine's maps ...
-    unsigned int *h_cen_flag = nullptr;   // ... and the sequence number of that copy (same allocation)
+    DevArray<uint32_t> d_census;     // [nmaps][256]
+    struct CensusRange { int v[2]; };
+    Published<CensusRange> h_cen;    // {min, max} over the engine's maps, and the sequence number of that copy
     unsigned int cen_seq = 0;
     float last_multiplier = 1.0f;    // what the last step used (ufm_heuristic_multiplier)
     void census_build(int m);
     void census_patch(int m, const uint8_t *dev_patch, int x, int y, int w, int h);
-    void census_publish() { k_census_publish<<<1, CENSUS_BINS, 0, stream>>>(d_census, nmaps, h_cen, h_cen_flag, ++cen_seq); }
+    void census_publish() { k_census_publish<<<1, CENSUS_BINS, 0, stream>>>(d_census, nmaps, h_cen->v, h_cen.flag(), ++cen_seq); }
     int census_minmax(int *mn, int *mx);
-    void census_free();
+    void census_free() { d_census.reset(); h_cen.reset(); census_on = auto_multiplier = false; }
     // Sensor reveal (ufm_set_sensor / ufm_set_survey / ufm_reveal; ufm_sensor.h).  No sensor and no survey -- the
     // default -- nothing below exists or runs.  d_lsurvey[k] holds what the sensor would see of layer k, per map (one layer: k = 0, the
     // map); a reveal makes the dense patch Q of every map's field of view in ONE launch (k_reveal, k_reveal_layers with more than one
     // layer) into that map's slot of d_reveal and hands the slot to route_patch().  A deferred patch may point into d_reveal: reveal()
     // applies what is held before the kernel writes the slots again.
     SensorShape sensor;
-    uint8_t *d_sensor = nullptr;     // the mask's bytes, room for SENSOR_MAX^2
-    uint8_t *d_lsurvey[LAYERS_MAX] = {nullptr, nullptr, nullptr, nullptr};   // [nmaps][L][W] each; dropped with the rasters (release())
+    DevArray<uint8_t> d_sensor;      // the mask's bytes, room for SENSOR_MAX^2
+    DevArray<uint8_t> d_lsurvey[LAYERS_MAX];     // [nmaps][L][W] each; dropped with the rasters (release())
     std::vector<uint8_t> have_lsurvey[LAYERS_MAX];   // [nmaps] each
     int survey_alloc(int k);
-    GrowBuf d_reveal;                // [nmaps] slots of sensor_slot_stride() bytes
-    unsigned int *d_reveal_cnt = nullptr;    // [nmaps]: changed cells of the last reveal
-    int32_t *h_centres = nullptr;    // [3 * nmaps], pinned + mapped: the centres as the reveal kernel reads them ([nmaps][2], with layers [nmaps][3])
+    ScratchBytes d_reveal;           // [nmaps] slots of sensor_slot_stride() bytes
+    DevArray<unsigned int> d_reveal_cnt;     // [nmaps]: changed cells of the last reveal
+    PinArray<int32_t> h_centres;     // [3 * nmaps], pinned + mapped: the centres as the reveal kernel reads them ([nmaps][2], with layers [nmaps][3])
     bool reveal_busy = false;        // a reveal kernel that is only queued may still read h_centres
     int reveal_check(const int32_t *centres) const;
     int reveal(const int32_t *centres);
@@ -318,18 +320,18 @@ struct Engine {
     // Map preparation (ufm_set_image; ufm_prepare.h).  Never called -- the default -- nothing below exists.  k_prepare
     // must not read what it writes: a host bitmap, or a device bitmap that overlaps the rasters, goes through this buffer, which is the
     // engine's and reused by every map, not kept per map.
-    GrowBuf d_image;
-    hipEvent_t prep_ev[2] = {nullptr, nullptr};   // profiling: on the k_prepare dispatch itself
+    ScratchBytes d_image;
+    EventSet<2> prep_ev;             // profiling: on the k_prepare dispatch itself
     float prep_ms = 0.0f;            // ... its duration (tools/prepare_probe.py)
     // Cost layers (ufm_set_layers / ufm_patch_layer / ufm_set_layer; ufm_layers.h).  n_layers == 1 -- the default --
     // nothing below exists or runs.  With more, d_layers holds n rasters per map and the caller's raster (d_raw with a footprint, P.cost
     // without) is their element-wise maximum between any two calls: a layer patch is stored, composed over its rectangle into the dense
     // d_lcomp and that one goes on as the caller's device patch would.  A reveal uncovers every layer that has a survey.
     int n_layers = 1;
-    uint8_t *d_layers = nullptr;     // [n_layers][nmaps] rasters at lstride bytes; dropped with the rasters (release())
+    DevArray<uint8_t> d_layers;      // [n_layers][nmaps] rasters at lstride bytes; dropped with the rasters (release())
     size_t lstride = 0;
-    GrowBuf d_lcomp;                 // the dense composed patch of the layer call being applied
-    hipEvent_t lay_ev[2] = {nullptr, nullptr};   // profiling: on the dispatch of the last layer kernel
+    ScratchBytes d_lcomp;            // the dense composed patch of the layer call being applied
+    EventSet<2> lay_ev;              // profiling: on the dispatch of the last layer kernel
     bool lay_timed = false;
     uint8_t *layer_ptr(int k, int m) const { return d_layers + layers_slot(k, m, nmaps, lstride); }
     int layer_surveys(int m) const {             // bit k: layer k of map m has a survey
@@ -341,16 +343,19 @@ struct Engine {
     int compose_layer(int k, const uint8_t *dev_patch, const PatchRect &r);
     // step deltas (ufm_track_changes / ufm_read_changes, ufm_delta.h): nothing below exists unless a caller turned tracking on
     bool track = false;
-    float *trk_g = nullptr;          // the baseline: the field as the caller was last told, in the layout of P.G (same gstride)
-    uint8_t *trk_key = nullptr;      // ... and (level 1/2) the key of every element's Info pair (info_from_byte, ufm_path.h)
-    void *trk_rec = nullptr;         // record buffer of the scan (DeltaRecords)
-    size_t trk_cap = 0;              // (records)
-    hipEvent_t trk_ev[2] = {nullptr, nullptr};
+    DevArray<float> trk_g;           // the baseline: the field as the caller was last told, in the layout of P.G (same gstride)
+    DevArray<uint8_t> trk_key;       // ... and (level 1/2) the key of every element's Info pair (info_from_byte, ufm_path.h)
+    GrowArray<uint8_t> trk_rec;      // record buffer of the scan (DeltaRecords): 256 bytes and 21 for each of ...
+    size_t trk_cap() const { return trk_rec.cap ? (trk_rec.cap - 256) / 21 : 0; }   // ... this many records
+    EventSet<2> trk_ev;
     float trk_scan_ms = 0.0f;        // profiling: duration of the last scan kernel
     int track_alloc();
     int track_reset(int m);
-    int track_records(size_t cap);
-    void track_free();
+    int track_records(size_t cap) { return trk_rec.reserve(stream, 256 + (cap + 63) / 64 * 64 * 21); }   // at least `cap` records
+    void track_free() {
+        if (trk_g || trk_rec.dev) hipStreamSynchronize(stream);
+        trk_g.reset(); trk_key.reset(); trk_rec.release();
+    }
 };
 
 void Engine::release() {
@@ -360,22 +365,60 @@ void Engine::release() {
     drop_graphs();                       // captured kernel arguments hold these pointers
     deferred.clear();
     std::memset(&graph_sig, 0, sizeof(graph_sig));
-    void *ptrs[] = {P.G, P.Gprev, P.bp, P.ring, P.cost, P.costT, P.goal, P.cand, P.ready, P.hint, P.rank, P.park, P.pflag, P.pprio,
-                    P.queued, P.prio, P.start, P.bnd, P.dyn, P.spos, P.touched, P.fresh, P.tlist, P.sflag, P.slist, P.slist2,
-                    P.mark, P.num_updated, P.consume, P.lmax, P.own_prio, P.own_lock, P.own_min, P.ctr, d_scratch};
-    for (void *q : ptrs) if (q) hipFree(q);
-    if (d_raw) hipFree(d_raw);
-    d_raw = nullptr;
-    if (d_layers) hipFree(d_layers);     // (the layers: rasters of these dimensions too)
-    d_layers = nullptr;
+    bufs.release();
+    d_raw.reset();
+    d_layers.reset();                    // (the layers: rasters of these dimensions too)
     for (int k = 0; k < LAYERS_MAX; ++k) {   // (a survey belongs to rasters of these dimensions)
-        if (d_lsurvey[k]) hipFree(d_lsurvey[k]);
-        d_lsurvey[k] = nullptr;
+        d_lsurvey[k].reset();
         std::fill(have_lsurvey[k].begin(), have_lsurvey[k].end(), (uint8_t)0);
     }
     P = DevParams{};                     // every pointer null again: a failed alloc() can be released, and released twice
-    d_scratch = nullptr;
     allocated = false;
+}
+
+// Every array DevParams points to, and d_scratch: one row each -- the field, its bytes, its first contents.  alloc() allocates and
+// fills from this table, release() frees what it got from it; the queue state (*: reset_queues()) is written there.
+std::vector<DevRow> Engine::buffer_rows() {
+    const size_t NT = (size_t)P.NT, n = (size_t)nmaps, gbytes = P.gstride * n * sizeof(float), I = sizeof(int);
+    return {
+        dev_row(P.G, gbytes, Fill::Inf),
+        dev_row(P.Gprev, gbytes, Fill::Inf),
+        dev_row(P.bp, P.gstride * n, Fill::BpNone),
+        dev_row(P.ring, NT * RING * sizeof(float), Fill::Inf),
+        dev_row(P.cost, P.cstride * n),
+        dev_row(P.costT, NT * CTS),
+        dev_row(P.goal, I * 2 * n, Fill::Ones),
+        // (the lists: a slot that was never written must still read as a tile id -- an in-launch reader may look at a slot its writer has claimed
+        //  but not yet stored, see the end check of k_replan_region)
+        dev_row(P.cand, I * 6 * NT, Fill::Zero),
+        dev_row(P.ready, I * NT, Fill::Zero),
+        dev_row(P.hint, I * NT, Fill::Zero),
+        dev_row(P.rank, I * NT, Fill::Zero),
+        dev_row(P.park, I * 4 * NT, Fill::Zero),
+        dev_row(P.pflag, I * 2 * NT),                                  // *
+        dev_row(P.pprio, I * 2 * NT),                                  // *
+        dev_row(P.queued, I * 4 * NT),                                 // *
+        dev_row(P.prio, sizeof(unsigned long long) * 4 * NT),          // *
+        dev_row(P.start, I * 4 * n, Fill::Ones),
+        dev_row(P.bnd, sizeof(float) * n),
+        dev_row(P.dyn, sizeof(DevDyn)),                                // (k_set_dyn, alloc())
+        dev_row(P.spos, sizeof(float) * 2 * n, Fill::Zero),
+        dev_row(P.touched, I * NT, Fill::Zero),
+        dev_row(P.fresh, NT, Fill::Zero),
+        dev_row(P.tlist, I * NT, Fill::Zero),
+        dev_row(P.sflag, I * NT, Fill::Zero),
+        dev_row(P.slist, I * NT, Fill::Zero),
+        dev_row(P.slist2, I * NT, Fill::Zero),
+        dev_row(P.mark, P.mstride * n, Fill::Zero),
+        dev_row(P.num_updated, sizeof(unsigned int) * n, Fill::Zero),
+        dev_row(P.consume, I * n),
+        dev_row(P.lmax, I * LMAX),
+        dev_row(P.own_prio, I * own_words()),                          // *
+        dev_row(P.own_lock, I * own_words()),                          // *
+        dev_row(P.own_min, I * OWN_NW),                                // *
+        dev_row(P.ctr, sizeof(DevCounters), Fill::Zero),               // (and *: its head)
+        dev_row(d_scratch, I * (4 * n + 16)),
+    };
 }
 
 int Engine::alloc(int width, int length) {
@@ -398,86 +441,26 @@ int Engine::alloc(int width, int length) {
     P.mstride = (size_t)P.EX * P.EY;
     own_layout(4);
     allocated = true;                    // from here on release() has something to free, also after a failure half way
-    const size_t gbytes = P.gstride * nmaps * sizeof(float);
-    int rc = UFM_OK;
-    auto dmalloc = [&](auto *&ptr, size_t bytes) {
-        if (rc != UFM_OK) return;
-        void *q = nullptr;
-        const hipError_t e = hipMalloc(&q, bytes ? bytes : 1);
-        if (e != hipSuccess) { (void)hipGetLastError(); rc = (e == hipErrorOutOfMemory) ? UFM_ERR_NOMEM : UFM_ERR_HIP_BASE - (int)e; return; }
-        ptr = static_cast<std::remove_reference_t<decltype(ptr)>>(q);
-    };
-    dmalloc(P.G, gbytes);
-    dmalloc(P.Gprev, gbytes);
-    dmalloc(P.bp, P.gstride * nmaps);
-    dmalloc(P.ring, (size_t)P.NT * RING * sizeof(float));
-    dmalloc(P.cost, P.cstride * nmaps);
-    dmalloc(P.costT, (size_t)P.NT * CTS);
-    dmalloc(P.goal, sizeof(int) * 2 * nmaps);
-    dmalloc(P.cand, sizeof(int) * 6 * P.NT);
-    dmalloc(P.ready, sizeof(int) * P.NT);
-    dmalloc(P.hint, sizeof(int) * P.NT);
-    dmalloc(P.rank, sizeof(int) * P.NT);
-    dmalloc(P.park, sizeof(int) * 4 * P.NT);
-    dmalloc(P.pflag, sizeof(int) * 2 * P.NT);
-    dmalloc(P.pprio, sizeof(int) * 2 * P.NT);
-    dmalloc(P.queued, sizeof(int) * 4 * P.NT);
-    dmalloc(P.prio, sizeof(unsigned long long) * 4 * P.NT);
-    dmalloc(P.start, sizeof(int) * 4 * nmaps);
-    dmalloc(P.bnd, sizeof(float) * nmaps);
-    dmalloc(P.dyn, sizeof(DevDyn));
-    dmalloc(P.spos, sizeof(float) * 2 * nmaps);
-    dmalloc(P.touched, sizeof(int) * P.NT);
-    dmalloc(P.fresh, (size_t)P.NT);
-    dmalloc(P.tlist, sizeof(int) * P.NT);
-    dmalloc(P.sflag, sizeof(int) * P.NT);
-    dmalloc(P.slist, sizeof(int) * P.NT);
-    dmalloc(P.slist2, sizeof(int) * P.NT);
-    dmalloc(P.mark, P.mstride * nmaps);
-    dmalloc(P.num_updated, sizeof(unsigned int) * nmaps);
-    dmalloc(P.consume, sizeof(int) * nmaps);
-    dmalloc(P.lmax, sizeof(int) * LMAX);
-    dmalloc(P.own_prio, sizeof(int) * own_words());
-    dmalloc(P.own_lock, sizeof(int) * own_words());
-    dmalloc(P.own_min, sizeof(int) * OWN_NW);
-    dmalloc(P.ctr, sizeof(DevCounters));
-    dmalloc(d_scratch, sizeof(int) * (4 * nmaps + 16));
-    if (cs.on) dmalloc(d_raw, P.cstride * nmaps);
-    if (n_layers > 1) { lstride = layers_stride(P.cstride); dmalloc(d_layers, lstride * nmaps * n_layers); }
-    if (rc != UFM_OK) { release(); return rc; }
-    rc = [&]() -> int {
-        // (the lists: a slot that was never written must still read as a tile id -- an in-launch reader may look at a slot its writer has claimed
-        //  but not yet stored, see the end check of k_replan_region)
-        HIPCHK(hipMemsetAsync(P.cand, 0, sizeof(int) * 6 * P.NT, stream));
-        HIPCHK(hipMemsetAsync(P.park, 0, sizeof(int) * 4 * P.NT, stream));
-        HIPCHK(hipMemsetAsync(P.ready, 0, sizeof(int) * P.NT, stream));
-        HIPCHK(hipMemsetAsync(P.tlist, 0, sizeof(int) * P.NT, stream));
-        HIPCHK(hipMemsetAsync(P.slist, 0, sizeof(int) * P.NT, stream));
-        HIPCHK(hipMemsetAsync(P.slist2, 0, sizeof(int) * P.NT, stream));
-        HIPCHK(hipMemsetAsync(P.rank, 0, sizeof(int) * P.NT, stream));
-        HIPCHK(hipMemsetAsync(P.hint, 0, sizeof(int) * P.NT, stream));
-        HIPCHK(hipMemsetAsync(P.spos, 0, sizeof(float) * 2 * nmaps, stream));
-        HIPCHK(hipMemsetAsync(P.start, 0xFF, sizeof(int) * 4 * nmaps, stream));
-        HIPCHK(hipMemsetAsync(P.ctr, 0, sizeof(DevCounters), stream));
-        { int rq = reset_queues(); if (rq != UFM_OK) return rq; }
-        HIPCHK(hipMemsetAsync(P.touched, 0, sizeof(int) * P.NT, stream));
-        HIPCHK(hipMemsetAsync(P.fresh, 0, (size_t)P.NT, stream));
-        HIPCHK(hipMemsetAsync(P.sflag, 0, sizeof(int) * P.NT, stream));
-        HIPCHK(hipMemsetAsync(P.mark, 0, P.mstride * nmaps, stream));
-        HIPCHK(hipMemsetAsync(P.num_updated, 0, sizeof(unsigned int) * nmaps, stream));
-        HIPCHK(hipMemsetAsync(P.goal, 0xFF, sizeof(int) * 2 * nmaps, stream));
-        if (d_layers) HIPCHK(hipMemsetAsync(d_layers, 0, lstride * nmaps * n_layers, stream));
-        k_fill<<<1024, 256, 0, stream>>>(P.G, P.gstride * nmaps, INFINITY);
-        k_fill<<<1024, 256, 0, stream>>>(P.Gprev, P.gstride * nmaps, INFINITY);
-        HIPCHK(hipMemsetAsync(P.bp, BP_NONE, P.gstride * nmaps, stream));
-        k_fill<<<1024, 256, 0, stream>>>(P.ring, (size_t)P.NT * RING, INFINITY);
+    const std::vector<DevRow> rows = buffer_rows();
+    const int rc = [&]() -> int {
+        { int ra = bufs.alloc(rows); if (ra != UFM_OK) return ra; }
+        if (cs.on) { int ra = d_raw.alloc(P.cstride * nmaps); if (ra != UFM_OK) return ra; }
+        if (n_layers > 1) {
+            lstride = layers_stride(P.cstride);
+            { int ra = d_layers.alloc(lstride * nmaps * n_layers); if (ra != UFM_OK) return ra; }
+            HIPCHK(hipMemsetAsync(d_layers, 0, lstride * nmaps * n_layers, stream));
+        }
+        for (const DevRow &r : rows) {
+            if (r.fill == Fill::Inf) k_fill<<<1024, 256, 0, stream>>>(static_cast<float *>(*r.field), r.bytes / sizeof(float), INFINITY);
+            else if (r.fill != Fill::None) HIPCHK(hipMemsetAsync(*r.field, r.fill == Fill::Zero ? 0 : (r.fill == Fill::Ones ? 0xFF : BP_NONE), r.bytes, stream));
+        }
+        { int rq = reset_queues(); if (rq != UFM_OK) return rq; }     // (behind the table's fills: it writes into the zeroed counter block)
         dyn_dev = DevDyn{heur ? heuristic_multiplier : 0.0f, thr_uchar, focused ? 1 : 0, 0};
         k_set_dyn<<<1, 1, 0, stream>>>(P.dyn, dyn_dev);
         HIPCHK(hipGetLastError());
-        return UFM_OK;
+        return track ? track_alloc() : UFM_OK;
     }();
     if (rc != UFM_OK) { release(); return rc; }
-    if (track) { rc = track_alloc(); if (rc != UFM_OK) { release(); return rc; } }
     pending.clear();
     for (auto &ms : maps) { ms.have_map = false; ms.initialize_search = true; }
     return UFM_OK;
@@ -531,12 +514,12 @@ int Engine::fetch_counters() {
         return UFM_OK;
     }
     ++pub_seq;
-    k_publish<<<1, 64, 0, stream>>>(P.ctr, h_ctr, h_flag, pub_seq);
+    k_publish<<<1, 64, 0, stream>>>(P.ctr, h_ctr, h_ctr.flag(), pub_seq);
     HIPCHK(hipGetLastError());
     return wait_published();
 }
 // spin until the device has published copy number pub_seq
-int Engine::wait_published() { return wait_flag(h_flag, pub_seq); }
+int Engine::wait_published() { return wait_flag(h_ctr.flag(), pub_seq); }
 int Engine::wait_flag(const unsigned int *flag, unsigned int seq) {
     const auto t0 = std::chrono::steady_clock::now();
     auto next_query = t0 + std::chrono::milliseconds(200);
@@ -587,7 +570,7 @@ int Engine::replan_graph(int nr, int nl, float band, hipGraphExec_t *out) {
     for (int i = 0; i < nr; ++i) relax(MODE_RAISE, false, dim3(std::min(grid_relax, grid_of(i))), -1 - i, INFINITY, -1.0f);
     k_raise_to_lower<<<1, 1024, 0, stream>>>(P, -1);
     for (int i = 0; i < nl; ++i) relax(MODE_LOWER, false, dim3(std::min(grid_relax, grid_of(i))), -1 - i, band_delta(delta_scale), INFINITY);
-    k_replan_end<<<64, T * T, 0, stream>>>(P, -1 - nr, -1 - nl, band, h_ctr, h_flag, 0u);
+    k_replan_end<<<64, T * T, 0, stream>>>(P, -1 - nr, -1 - nl, band, h_ctr, h_ctr.flag(), 0u);
     finalize_bp(1);     // (behind the publication: the host does not wait for it, the next step's kernels do)
     hipGraph_t g = nullptr;
     HIPCHK(hipStreamEndCapture(stream, &g));
@@ -646,7 +629,7 @@ int Engine::owned_phase() {
     const dim3 g(P.own_nw), b(half ? NTHR / 2 : NTHR);
     own_timed = false;
     if (profiling) {
-        for (auto &e : own_ev) if (!e) HIPCHK(hipEventCreate(&e));
+        { int rc = own_ev.ensure(); if (rc != UFM_OK) return rc; }
         own_timed = true;
     }
     hipEvent_t e0 = own_timed ? own_ev[0] : nullptr, e1 = own_timed ? own_ev[1] : nullptr;
@@ -680,7 +663,7 @@ int Engine::run_phase(int mode, float rbound, uint32_t *launches, float *kernel_
     // pipelined: batch b + 1 is submitted before the counters batch b published are looked at; otherwise the host waits for every batch
     const bool pipelined = spin_wait && pipeline_batches && h_pipe_ctr[0];
     batch_ev_slot = 2 * std::max(32, batch_fixed);     // events per batch: two per launch (adaptive batches: <= 32 launches)
-    while (profiling && batch_ev.size() < (size_t)((pipelined ? 2 : 1) * batch_ev_slot)) { hipEvent_t a; HIPCHK(hipEventCreate(&a)); batch_ev.push_back(a); }
+    while (profiling && batch_ev.size() < (size_t)((pipelined ? 2 : 1) * batch_ev_slot)) { EventSet<1> a; int rc = a.ensure(); if (rc != UFM_OK) return rc; batch_ev.push_back(std::move(a)); }
     struct Batch { unsigned int seq; int slot, ns, iter_after; };
     auto counters = [&](const Batch &b) -> const DevCounters * { return pipelined ? h_pipe_ctr[b.slot] : h_ctr; };
     long total = 0;
@@ -688,10 +671,10 @@ int Engine::run_phase(int mode, float rbound, uint32_t *launches, float *kernel_
         int ns = 0;
         for (int k = 0; k < n; ++k) {
             const bool timed_k = profiling && ((total + k) % profile_stride == 0);
-            launch_relax(mode, rbound, timed_k ? *batch_event(slot, 2 * ns) : nullptr, timed_k ? *batch_event(slot, 2 * ns + 1) : nullptr);
+            launch_relax(mode, rbound, timed_k ? batch_event(slot, 2 * ns) : nullptr, timed_k ? batch_event(slot, 2 * ns + 1) : nullptr);
             if (timed_k) ++ns;
         }
-        if (pipelined) k_publish<<<1, 64, 0, stream>>>(P.ctr, h_pipe_ctr[slot], h_pipe_flag[slot], ++pub_seq);
+        if (pipelined) k_publish<<<1, 64, 0, stream>>>(P.ctr, h_pipe_ctr[slot], h_pipe_ctr[slot].flag(), ++pub_seq);
         HIPCHK(hipGetLastError());
         *b = {pub_seq, slot, ns, iter[q]};
         *launches += (uint32_t)n;
@@ -699,11 +682,11 @@ int Engine::run_phase(int mode, float rbound, uint32_t *launches, float *kernel_
         return UFM_OK;
     };
     auto collect = [&](const Batch &b) -> int {               // wait for the batch's counters, add its timed launches
-        int rc = pipelined ? wait_flag(h_pipe_flag[b.slot], b.seq) : fetch_counters();
+        int rc = pipelined ? wait_flag(h_pipe_ctr[b.slot].flag(), b.seq) : fetch_counters();
         if (rc != UFM_OK) return rc;
         for (int k = 0; k < b.ns; ++k) {
             float ms = 0;
-            HIPCHK(hipEventElapsedTime(&ms, *batch_event(b.slot, 2 * k), *batch_event(b.slot, 2 * k + 1)));
+            HIPCHK(hipEventElapsedTime(&ms, batch_event(b.slot, 2 * k), batch_event(b.slot, 2 * k + 1)));
             *kernel_ms += ms;
         }
         *timed += (uint32_t)b.ns;
@@ -826,7 +809,7 @@ int Engine::begin_step(StepRun &r) {
 // the device-side end check of a fused submission (k_replan_end publishes the counters), the back-pointers behind it
 int Engine::fused_end(float band) {
     ++pub_seq;
-    k_replan_end<<<64, T * T, 0, stream>>>(P, iter[Q_RAISE], iter[Q_LOWER], band, h_ctr, h_flag, pub_seq);
+    k_replan_end<<<64, T * T, 0, stream>>>(P, iter[Q_RAISE], iter[Q_LOWER], band, h_ctr, h_ctr.flag(), pub_seq);
     finalize_bp(1);     // (behind the publication: the host does not wait for it, the next step's kernels do)
     HIPCHK(hipGetLastError());
     return wait_published();
@@ -870,12 +853,12 @@ int Engine::submit_block(StepRun &r) {
     if (batch) flush_dyn(r);
     else { dyn_dev = r.dyn_now; r.dyn_pending = false; }
     const bool reg_timed = profiling && (region_runs & 7u) == 0u;     // a sample: the event packets cost a few microseconds each
-    if (reg_timed) for (auto &e : reg_ev) if (!e) HIPCHK(hipEventCreate(&e));
+    if (reg_timed) { int rc = reg_ev.ensure(); if (rc != UFM_OK) return rc; }
     // the kernel's form (ufm_region.h, RF_*): the diagnostics bring everything with them; otherwise the heuristic term only where the keys have one
     const int form = region_debug ? (RF_HEUR | RF_DEBUG) : (r.dyn_now.hm != 0.0f ? RF_HEUR : 0);
     with_raise_op(algo, dfm_follow_info, [&](auto a) {
         auto go = [&](auto f) {
-            launch(k_replan_region<a(), f()>, dim3(rjs.n), dim3(NTHR), stream, reg_timed ? reg_ev[0] : nullptr, reg_timed ? reg_ev[1] : nullptr, P, rjs, h_ctr, h_flag);
+            launch(k_replan_region<a(), f()>, dim3(rjs.n), dim3(NTHR), stream, reg_timed ? reg_ev[0] : nullptr, reg_timed ? reg_ev[1] : nullptr, P, rjs, h_ctr, h_ctr.flag());
         };
         if (form == 0) go(IntC<0>{});
         else if (form == RF_HEUR) go(IntC<RF_HEUR>{});
@@ -956,9 +939,9 @@ int Engine::submit_chain(StepRun &r) {
         k_prepare_bound<<<1, 64, 0, stream>>>(P, r.band);
         k_unpark<<<1, 1024, 0, stream>>>(P, Q_RAISE, iter[Q_RAISE], -1.0f);
     }
-    hipEvent_t *e = chain_ev;
+    const EventSet<4> &e = chain_ev;
     if (profiling) {
-        for (auto &v : chain_ev) if (!v) HIPCHK(hipEventCreate(&v));
+        { int rc = chain_ev.ensure(); if (rc != UFM_OK) return rc; }
         HIPCHK(hipEventRecord(e[0], stream));
     }
     last_active = 1;             // replans touch a handful of tiles: fused triage
@@ -1199,7 +1182,7 @@ int engine_create(Engine **out, int n_maps, int algo, int opt_lvl, int use_heuri
     HIPCHK(hipGetDeviceCount(&ndev));
     if (device_id < 0 || device_id >= ndev) return UFM_ERR_INVALID;
     HIPCHK(hipSetDevice(device_id));
-    Engine *e = new (std::nothrow) Engine();
+    std::unique_ptr<Engine> e(new (std::nothrow) Engine());   // every early return below frees what has been made so far
     if (!e) return UFM_ERR_NOMEM;
     e->algo = algo; e->opt_lvl = opt_lvl; e->heur = use_heuristic; e->device = device_id; e->nmaps = n_maps;
     // scheduling defaults per planner family (tools/sweep.py, 4096^2): DFM's two-stencil operator needs about
@@ -1212,32 +1195,16 @@ int engine_create(Engine **out, int n_maps, int algo, int opt_lvl, int use_heuri
     HIPCHK(hipGetDeviceProperties(&prop, device_id));
     e->grid_relax = prop.multiProcessorCount * 2;
     e->dyn_grid = prop.multiProcessorCount;
-    HIPCHK(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
-    {   // counters + sequence flag in one host-coherent, device-mapped allocation
-        const size_t flag_off = (sizeof(DevCounters) + 63) / 64 * 64;
-        void *pub = nullptr;
-        HIPCHK(hipHostMalloc(&pub, flag_off + 64, hipHostMallocMapped | hipHostMallocCoherent));
-        std::memset(pub, 0, flag_off + 64);
-        e->h_ctr = static_cast<DevCounters *>(pub);
-        e->h_flag = reinterpret_cast<unsigned int *>(static_cast<char *>(pub) + flag_off);
-        for (int i = 0; i < 2; ++i) {
-            void *pp = nullptr;
-            HIPCHK(hipHostMalloc(&pp, flag_off + 64, hipHostMallocMapped | hipHostMallocCoherent));
-            std::memset(pp, 0, flag_off + 64);
-            e->h_pipe_ctr[i] = static_cast<DevCounters *>(pp);
-            e->h_pipe_flag[i] = reinterpret_cast<unsigned int *>(static_cast<char *>(pp) + flag_off);
-        }
-        void *job = nullptr;
-        HIPCHK(hipHostMalloc(&job, sizeof(ReplanJob), hipHostMallocMapped | hipHostMallocCoherent));
-        std::memset(job, 0, sizeof(ReplanJob));
-        e->h_job = static_cast<ReplanJob *>(job);
-    }
+    HIPCHK(hipStreamCreateWithFlags(&e->stream.s, hipStreamNonBlocking));
+    for (Published<DevCounters> *pub : {&e->h_ctr, &e->h_pipe_ctr[0], &e->h_pipe_ctr[1]}) { int rc = pub->alloc(); if (rc != UFM_OK) return rc; }
+    { int rc = e->h_job.alloc(1, Pin::Coherent); if (rc != UFM_OK) return rc; }
+    std::memset(e->h_job, 0, sizeof(ReplanJob));
     {   // The first graph a process captures and instantiates costs ~8 ms of one-time set-up inside the
         // runtime; pay it here, not in the first replan (a planner is created outside any timed step).
         hipGraph_t g = nullptr;
         hipGraphExec_t ge = nullptr;
         if (hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-            k_fill<<<1, 64, 0, e->stream>>>(reinterpret_cast<float *>(e->h_job), 0, 0.0f);
+            k_fill<<<1, 64, 0, e->stream>>>(reinterpret_cast<float *>(e->h_job.p), 0, 0.0f);
             if (hipStreamEndCapture(e->stream, &g) == hipSuccess && g) {
                 if (hipGraphInstantiate(&ge, g, nullptr, nullptr, 0) == hipSuccess && ge) {
                     (void)hipGraphLaunch(ge, e->stream);
@@ -1250,32 +1217,13 @@ int engine_create(Engine **out, int n_maps, int algo, int opt_lvl, int use_heuri
         (void)hipGetLastError();
     }
     { int rc = e->scratch.carve(n_maps); if (rc != UFM_OK) return rc; }
-    HIPCHK(hipHostMalloc(&e->h_bnd, sizeof(float) * n_maps));
-    *out = e;
+    { int rc = e->h_bnd.alloc(n_maps); if (rc != UFM_OK) return rc; }
+    *out = e.release();
     return UFM_OK;
 }
 
-int engine_destroy(Engine *e) {
+int engine_destroy(Engine *e) {     // ~Engine waits for the stream and drops the graphs; the members' order does the rest
     if (!e) return UFM_ERR_INVALID;
-    hipSetDevice(e->device);
-    if (e->stream) hipStreamSynchronize(e->stream);
-    e->release();
-    for (hipEvent_t v : e->batch_ev) hipEventDestroy(v);
-    for (hipEvent_t v : e->chain_ev) if (v) hipEventDestroy(v);
-    for (hipEvent_t v : e->own_ev) if (v) hipEventDestroy(v);
-    for (hipEvent_t v : e->reg_ev) if (v) hipEventDestroy(v);
-    for (hipEvent_t v : e->trk_ev) if (v) hipEventDestroy(v);
-    for (hipEvent_t v : e->prep_ev) if (v) hipEventDestroy(v);
-    e->census_free();
-    free_all(hipFree, e->d_sensor, e->d_reveal_cnt);
-    free_all(hipHostFree, e->h_centres);
-    for (hipEvent_t v : e->lay_ev) if (v) hipEventDestroy(v);
-    for (GrowBuf *b : {&e->d_patch, &e->d_pmask, &e->d_cs_patch, &e->d_reveal, &e->d_image, &e->d_lcomp}) b->release();
-    free_all(hipFree, e->d_field, e->d_info, e->d_jobs, e->d_path);
-    free_all(hipHostFree, e->h_jobs, e->h_path, e->h_lazy);
-    e->drop_graphs();
-    free_all(hipHostFree, e->h_ctr, e->h_pipe_ctr[0], e->h_pipe_ctr[1], e->h_job, e->scratch.acc, e->h_bnd);
-    if (e->stream) hipStreamDestroy(e->stream);
     delete e;
     return UFM_OK;
 }
@@ -1300,9 +1248,7 @@ int engine_read_field(Engine *e, int m, int x0, int y0, int nx, int ny, float *g
     if (!dst) return UFM_OK;
     // the field is tile-major on the device: gather the window into a dense buffer, then one copy
     const size_t n = (size_t)nx * ny;
-    if (n > e->d_field_cap) {
-        { int rc = regrow(e->stream, n * sizeof(float), e->d_field_cap, n, e->d_field); if (rc != UFM_OK) return rc; }
-    }
+    { int rc = e->d_field.reserve(e->stream, n); if (rc != UFM_OK) return rc; }
     k_gather_field<<<(unsigned)std::min<size_t>((n + 255) / 256, 65535), 256, 0, e->stream>>>(e->P, m, x0, y0, nx, ny, e->d_field);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(dst, e->d_field, n * sizeof(float), hipMemcpyDeviceToHost, e->stream));
@@ -1336,28 +1282,26 @@ int engine_walk(Engine *e, const PathQuery *q, size_t n, int max_steps, int look
     const int dev_pts = std::min(cap_pts, 3 * max_steps + 1), dev_cst = std::min(cap_costs, 2 * max_steps);
     const size_t ostride = PATH_HDR + 2 * (size_t)dev_pts + dev_cst;
     const size_t chunk = std::min(n, std::min(PATH_CHUNK_JOBS, std::max<size_t>(PATH_CHUNK_FLOATS / ostride, 1)));
-    if (ostride * chunk > e->path_cap) {
-        { int rc = regrow(e->stream, ostride * chunk * sizeof(float), e->path_cap, ostride * chunk, e->d_path, &e->h_path, true); if (rc != UFM_OK) return rc; }
-    }
-    if (chunk > e->jobs_cap) {
-        { int rc = regrow(e->stream, sizeof(PathJob) * chunk, e->jobs_cap, chunk, e->d_jobs, &e->h_jobs, true); if (rc != UFM_OK) return rc; }
-    }
+    { int rc = e->d_path.reserve(e->stream, ostride * chunk, true, true); if (rc != UFM_OK) return rc; }
+    { int rc = e->d_jobs.reserve(e->stream, chunk, true, true); if (rc != UFM_OK) return rc; }
+    PathJob *h_jobs = e->d_jobs.pinned;
+    const float *h_path = e->d_path.pinned;
     PathField F = path_field(e, 0);     // (the walks' jobs name their maps)
     F.indirect = allow_indirect != 0;
     for (size_t first = 0; first < n; first += chunk) {
         const size_t cnt = std::min(chunk, n - first);
         for (size_t k = 0; k < cnt; ++k) {      // (the pinned buffers are free again: every chunk ends with a wait for the stream)
             const PathQuery &w = q[first + k];
-            e->h_jobs[k] = PathJob{w.sx, w.sy, e->maps[w.m].goal_x, e->maps[w.m].goal_y, w.m};
+            h_jobs[k] = PathJob{w.sx, w.sy, e->maps[w.m].goal_x, e->maps[w.m].goal_y, w.m};
         }
-        HIPCHK(hipMemcpyAsync(e->d_jobs, e->h_jobs, sizeof(PathJob) * cnt, hipMemcpyHostToDevice, e->stream));
+        HIPCHK(hipMemcpyAsync(e->d_jobs, h_jobs, sizeof(PathJob) * cnt, hipMemcpyHostToDevice, e->stream));
         k_extract_path<<<(unsigned)cnt, 64, 0, e->stream>>>(F, e->P.gstride, e->P.cstride, e->d_jobs, e->d_path, ostride,
                                                             dev_pts, dev_cst, lookahead != 0, max_steps);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(e->h_path, e->d_path, ostride * cnt * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipMemcpyAsync(e->d_path.pinned, e->d_path, ostride * cnt * sizeof(float), hipMemcpyDeviceToHost, e->stream));
         HIPCHK(hipStreamSynchronize(e->stream));
         for (size_t k = 0; k < cnt; ++k) {
-            const float *o = e->h_path + ostride * k;
+            const float *o = h_path + ostride * k;
             const size_t slot = q[first + k].slot;
             ufm_path_info &pi = info[slot];
             std::memcpy(&pi.n_points, &o[0], 4);
@@ -1430,9 +1374,7 @@ int engine_read_queue(Engine *e, int m, int cap, int32_t *xy, float *g_rhs, int 
     HIPCHK(hipSetDevice(e->device));
     { int rc = e->flush_deferred(); if (rc != UFM_OK) return rc; }   // (the derived RHS / the stored bytes' view read the raster)
     const size_t words = (size_t)std::max(cap, 1) * 4 + 1;          // [cap][2] int32, [cap][2] float, the count
-    if (words > e->d_info_cap) {
-        { int rc = regrow(e->stream, words * sizeof(int32_t), e->d_info_cap, words, e->d_info); if (rc != UFM_OK) return rc; }
-    }
+    { int rc = e->d_info.reserve(e->stream, words); if (rc != UFM_OK) return rc; }
     int32_t *d_xy = e->d_info;
     float *d_gr = reinterpret_cast<float *>(e->d_info + (size_t)std::max(cap, 1) * 2);
     unsigned int *d_cnt = reinterpret_cast<unsigned int *>(e->d_info + (size_t)std::max(cap, 1) * 4);
@@ -1465,9 +1407,7 @@ int engine_read_info(Engine *e, int m, int x0, int y0, int nx, int ny, int32_t *
     HIPCHK(hipSetDevice(e->device));
     { int rc = e->flush_deferred(); if (rc != UFM_OK) return rc; }   // (the derived RHS / the stored bytes' view read the raster)
     const size_t n = (size_t)nx * ny;
-    if (n * 2 > e->d_info_cap) {        // device buffer kept between calls (a consumer asks window after window)
-        { int rc = regrow(e->stream, n * 2 * sizeof(int32_t), e->d_info_cap, n * 2, e->d_info); if (rc != UFM_OK) return rc; }
-    }
+    { int rc = e->d_info.reserve(e->stream, n * 2); if (rc != UFM_OK) return rc; }     // (kept between calls: a consumer asks window after window)
     int32_t *d_out = e->d_info;
     const PathField F = path_field(e, m);
     if (derived) k_info<<<(unsigned)((n + 255) / 256), 256, 0, e->stream>>>(F, e->opt_lvl, x0, y0, nx, ny, d_out);

@@ -44,7 +44,7 @@ int Engine::flush_lazy() {
 }
 // way Hold: the bytes into the next pinned slot, the rectangle to the pending ones
 int Engine::hold_host_patch(const PatchRect &r, const uint8_t *host_patch) {
-    if (!h_lazy) HIPCHK(hipHostMalloc(&h_lazy, (size_t)LAZY_SLOTS * 4096, hipHostMallocMapped));
+    { int rc = h_lazy.ensure((size_t)LAZY_SLOTS * 4096, Pin::Mapped); if (rc != UFM_OK) return rc; }
     // (a slot is free again when the step that consumed its patch has returned -- step() is synchronous -- or when flush_lazy() has run and the
     //  stream has been waited for; slots are handed out in order, so the one after the last held patch's is the oldest)
     const int slot = lazy.empty() ? (lazy_next % LAZY_SLOTS) : ((lazy.back().slot + 1) % LAZY_SLOTS);
@@ -167,15 +167,9 @@ void Engine::census_patch(int m, const uint8_t *dev_patch, int x, int y, int w, 
 // the published range as of the last build or patch queued: the host waits for that copy's sequence number (nothing is held while the census is on)
 int Engine::census_minmax(int *mn, int *mx) {
     if (!census_on) return UFM_ERR_INVALID;
-    { int rc = wait_flag(h_cen_flag, cen_seq); if (rc != UFM_OK) return rc; }
-    *mn = h_cen[0]; *mx = h_cen[1];
+    { int rc = wait_flag(h_cen.flag(), cen_seq); if (rc != UFM_OK) return rc; }
+    *mn = h_cen->v[0]; *mx = h_cen->v[1];
     return UFM_OK;
-}
-void Engine::census_free() {
-    if (d_census) hipFree(d_census);
-    if (h_cen) hipHostFree(h_cen);
-    d_census = nullptr; h_cen = nullptr; h_cen_flag = nullptr;
-    census_on = auto_multiplier = false;
 }
 // ufm_track_costs / ufm_batch_track_costs.  On, with maps already set: what is held is applied and the counters are built from the rasters
 // as they stand.  Off frees everything; refused while "auto_multiplier" is 1 (the step would have nothing to take).
@@ -192,12 +186,8 @@ int engine_track_costs(Engine *e, int enable) {
     if (e->census_on) return UFM_OK;
     if (e->allocated) { int rc = e->flush_deferred(); if (rc != UFM_OK) return rc; }
     const int rc = [&]() -> int {
-        HIPCHK(hipMalloc(&e->d_census, sizeof(uint32_t) * CENSUS_BINS * e->nmaps));
-        void *pub = nullptr;
-        HIPCHK(hipHostMalloc(&pub, 128, hipHostMallocMapped | hipHostMallocCoherent));
-        std::memset(pub, 0, 128);
-        e->h_cen = static_cast<int *>(pub);
-        e->h_cen_flag = reinterpret_cast<unsigned int *>(static_cast<char *>(pub) + 64);
+        { int ra = e->d_census.alloc((size_t)CENSUS_BINS * e->nmaps); if (ra != UFM_OK) return ra; }
+        { int ra = e->h_cen.alloc(); if (ra != UFM_OK) return ra; }
         e->cen_seq = 0;
         HIPCHK(hipMemsetAsync(e->d_census, 0, sizeof(uint32_t) * CENSUS_BINS * e->nmaps, e->stream));
         for (int m = 0; m < e->nmaps; ++m) if (e->allocated && e->maps[m].have_map) e->census_build(m);
@@ -225,7 +215,7 @@ int Engine::layer_events(hipEvent_t *e0, hipEvent_t *e1) {
     *e0 = *e1 = nullptr;
     lay_timed = false;
     if (!profiling) return UFM_OK;
-    for (auto &e : lay_ev) if (!e) HIPCHK(hipEventCreate(&e));
+    { int rc = lay_ev.ensure(); if (rc != UFM_OK) return rc; }
     *e0 = lay_ev[0]; *e1 = lay_ev[1];
     lay_timed = true;
     return UFM_OK;
@@ -283,7 +273,7 @@ int engine_read_layer(Engine *e, int m, int k, uint8_t *out) {
 // ---- surveys: what the sensor would see of layer k of map m, for the raster that map has (one layer: k = 0, the map) ----
 int Engine::survey_alloc(int k) {
     if (d_lsurvey[k]) return UFM_OK;
-    if (hipMalloc(&d_lsurvey[k], P.cstride * nmaps) != hipSuccess) { (void)hipGetLastError(); d_lsurvey[k] = nullptr; return UFM_ERR_NOMEM; }
+    { int rc = d_lsurvey[k].alloc(P.cstride * nmaps); if (rc != UFM_OK) return rc; }
     have_lsurvey[k].assign((size_t)nmaps, 0);
     return UFM_OK;
 }
@@ -316,18 +306,11 @@ int engine_set_sensor(Engine *e, const uint8_t *mask, int mw, int mh, int ar, in
     SensorShape s;
     if (!sensor_pack(mask, mw, mh, ar, ac, &s)) return UFM_ERR_INVALID;
     HIPCHK(hipSetDevice(e->device));
-    if (!e->d_sensor) {
-        const int rc = [&]() -> int {
-            HIPCHK(hipMalloc(&e->d_sensor, (size_t)SENSOR_MAX * SENSOR_MAX));
-            HIPCHK(hipMalloc(&e->d_reveal_cnt, sizeof(unsigned int) * e->nmaps));
-            HIPCHK(hipHostMalloc(&e->h_centres, sizeof(int32_t) * 3 * e->nmaps, hipHostMallocMapped));
-            return UFM_OK;
-        }();
-        if (rc != UFM_OK) {
-            free_all(hipFree, e->d_sensor, e->d_reveal_cnt); free_all(hipHostFree, e->h_centres);
-            e->d_sensor = nullptr; e->d_reveal_cnt = nullptr; e->h_centres = nullptr;
-            return rc;
-        }
+    {   // (each allocated once: a call that fails half way leaves owned buffers, and the next one makes the rest)
+        int rc = e->d_sensor.ensure((size_t)SENSOR_MAX * SENSOR_MAX);
+        if (rc == UFM_OK) rc = e->d_reveal_cnt.ensure((size_t)e->nmaps);
+        if (rc == UFM_OK) rc = e->h_centres.ensure(3 * (size_t)e->nmaps, Pin::Mapped);
+        if (rc != UFM_OK) return rc;
     }
     // (a reveal that is only queued reads the old mask: wait for it, then replace the bytes)
     HIPCHK(hipStreamSynchronize(e->stream));
@@ -485,7 +468,7 @@ int engine_set_image(Engine *e, int m, const uint8_t *src, bool on_device, int w
         j.wide_out = width % 4 == 0 && prep_aligned4(j.out_l) && prep_aligned4(j.out_h);
         j.taps = k;
         timed = e->profiling;
-        if (timed && !e->prep_ev[0]) { HIPCHK(hipEventCreate(&e->prep_ev[0])); HIPCHK(hipEventCreate(&e->prep_ev[1])); }
+        if (timed) { int rc2 = e->prep_ev.ensure(); if (rc2 != UFM_OK) return rc2; }
         launch(k_prepare, dim3(prep_grid_x(width), prep_grid_y(length)), dim3(PREP_THREADS), e->stream, timed ? e->prep_ev[0] : nullptr,
                timed ? e->prep_ev[1] : nullptr, j);
         HIPCHK(hipGetLastError());
