@@ -73,7 +73,9 @@ struct StreamOwner {                             // the engine's stream: its fir
     operator hipStream_t() const { return s; }
 };
 
-struct Engine {
+#include "ufm_knobs.h"
+
+struct Engine : Knobs {     // the tuning members -- what ufm_set_param sets -- are Knobs' (ufm_knobs.h)
     StreamOwner stream;              // declared first, destroyed last: behind every buffer and event below
     ~Engine() {                      // the members give back what they own, in reverse order; first nothing may be running or hold their pointers
         hipSetDevice(device);
@@ -92,38 +94,13 @@ struct Engine {
     Published<DevCounters> h_ctr;    // k_publish writes it, the host spins on h_ctr.flag(): the sequence number of the last published copy
     Published<DevCounters> h_pipe_ctr[2];   // run_phase keeps one batch of launches in flight ahead of the one whose
                                             // counters it is looking at: two more published copies, used alternately
-    bool pipeline_batches = true;
     unsigned int pub_seq = 0;
-    bool spin_wait = true;           // false: hipMemcpyAsync + hipStreamSynchronize instead
-    bool fuse_control = true;        // replans: fused control kernels (k_replan_begin / _raise_to_lower / _end)
-    bool use_graph = true;           // replans: the whole submission replayed as one captured hipGraph
-    bool use_owned = true;           // plans: the lowering phase as ONE resident launch (k_relax<.,LOWER,false,1|2>) instead of a launch per band step
-    float owned_limit_ms = -1.0f;    // ... which hands back to the launch chain after this long, whatever happens (< 0: by the size of the job,
-                                     //     ~15 x what a plan of that many tiles takes: a device shared with another long-running kernel)
-    float owned_band = -1.0f;        // ... ordering band in tile crossings (< 0: by the job -- 2.5 for a single map of a node planner, 3 for MS-DFM, 2 for a batch: owned_phase())
     uint32_t owned_launches = 0;
     EventSet<2> own_ev;
     EventSet<2> reg_ev;              // profiling: around the block kernel of a replan
     bool own_timed = false;
-    int owned_flags = 0;             // resident kernel, diagnostics and variants.  1: no tile taken ahead; 2: no early hand-off (FD / SG); 4: early hand-off once per patch and visit;
-                                     // 8: early hand-off waits for its stores inside the sweep loop; 16: no in-visit halo refresh; 32: idle workgroups do not help out;
-                                     // 64: a workgroup does not follow the front (the neighbour it has just queued); 128: ... follows it beyond the ordering band too
-    int owned_waves = 0;             // waves per tile visit of the resident kernel: 16 (256 workgroups), 8 (512), 0 = by the size of the job
-    bool dfm_follow_info = false;    // MS-DFM level 1: the invalidation follows the stored back-pointer bytes (k_relax / k_replan_region<ALGO_DFM1_INFO>)
-    bool use_region = true;          // replans: one workgroup runs both phases in LDS on the block around the patch (ufm_region.h);
-                                     // the launch chain only takes over when work is left outside the block
-    int region_ahead = 2;            // block placement: tiles kept between the patches' centre and the block's goal-side edge
-    int region_tiles = 6;            // block edge in tiles (<= RTMAX; measured on the headline replans: 10 -> 6 tiles: 20.0 -> 18.6 ms per 100, same completion rate)
-    int region_sweeps = 4096;        // sweep budget per wave and phase
-    int region_debug = 0;
-    float region_band = 1.5f;        // ordering band of the block's lowering sub-rounds, in patch crossings at the mean cost (0: unordered)
     uint32_t region_runs = 0, region_done = 0;   // replans submitted to the block kernel / completed by it alone
     uint32_t region_cont = 0, region_cont_done = 0;   // ... continued by one blind submission of the launch chain / completed by that
-    int cont_raise = 4, cont_lower = 8;          // launches of that submission per phase (0: straight to the adaptive loop -- MS-DFM, whose leftovers are
-                                                 // chains of 20-40 band steps, mostly invalidation: measured, config 4, 903 us per such round either way;
-                                                 // sending the leftover lowering through the resident kernel instead: 1 111 us)
-    int batch_margin = 1;            // replans: launches per phase = most that the last 6 replans needed + this
-    float raise_margin = 0.25f;      // invalidation bound = start key + this many ordering bands (a miss costs a second round)
     PinArray<ReplanJob> h_job;       // host-coherent pinned: per-replan inputs of the graph's first node
     struct GraphSig { DevParams P; float band, delta; int max_iters, grid, follow; };
     GraphSig graph_sig{};
@@ -134,7 +111,6 @@ struct Engine {
         if (algo == UFM_ALGO_DFM && opt_lvl < 1) return;
         with_lower_op(algo, [&](auto a) { k_finalize_bp<a()><<<2048, 256, 0, stream>>>(P, only_if_done); });
     }
-    int tail_grid = 96;              // replan graph: workgroups of the later launches of a phase (few tiles left)
     int replan_graph(int nr, int nl, float band, hipGraphExec_t *out);
     void drop_graphs() { for (auto &g : graphs) hipGraphExecDestroy(g.second); graphs.clear(); }
     struct StepScratch {             // pinned: 2 accumulators + 12 * nmaps ints, one allocation carved once (engine_create)
@@ -160,24 +136,9 @@ struct Engine {
     std::vector<MapState> maps;
     std::vector<PatchRect> pending;
     int iter[2] = {0, 0};            // index k of the next relax launch of each queue (never reset: the queues persist)
-    bool focused = true;             // stop at the start's key like the reference (end_condition)
-    bool start_cell_floor = false;   // start_cell_ = the cell that contains the start position (floor) instead of Cell(Position)'s roundf (Cell.cpp:20-21): what the
-                                     // revision of the reference that wrote its two recorded mission logs did (tests/test_reference_mission.py; oracle: ORC_REV_LOG)
-    bool dynamic_mode = true;        // long queues: k_triage + cursor hand-out
     PinArray<float> h_bnd;           // pinned [nmaps]
     int last_active = 1;             // queue length at the last host check: long queues go through k_triage
-    int grid_relax = 512;
-    int dyn_grid = 256;              // workgroups of a cursor hand-out launch: the number of CUs
-    int small_grid = 1 << 30;        // workgroups of a relax launch over a short queue (measured: no gain, off)
-    int max_iters = 32;              // sweep cap per tile visit (x4 patch sweeps per wave): a tile that needs more is
-                                     // re-queued instead of holding the whole launch (measured optimum on 4096^2)
-    float delta_abs = -1.0f;         // ordering band; < 0: delta_scale * T * mean traversable cost
-    float delta_scale = 1.5f;
-    float delta_scale_long = 2.0f;   // ... for long queues (the plans' cursor hand-out launches): a wider band, fewer band steps
-                                     // (tools/sweep.py on the final scheduler: plan 24.2 ms at 1.5, 23.6 at 2.0, 23.9 at 2.5;
-                                     //  the replans' short launches are best at 1.5)
     float mean_cost = 1.0f;
-    int batch_fixed = 0;
     bool profiling = false;
     EventSet<4> chain_ev;            // profiling: around the two blind batches of a replan's launch chain
     std::vector<EventSet<1>> batch_ev;    // ... and the sampled launches of run_phase's batches, batch_ev_slot events per batch in flight
@@ -204,7 +165,6 @@ struct Engine {
         const size_t sx = (size_t)(P.TX + 15) / 16;
         return (size_t)nmaps * sx * std::max<size_t>(256 * (size_t)((P.TY + 15) / 16), 512 * (size_t)((P.TY + 31) / 32));
     }
-    int profile_stride = 4;          // profiling: every n-th launch of a plan is bracketed by events
     int reset_queues();
     int read_bounds(float *bmax);
     // a step (ReplannerBase::step) and its parts, in the order they run; StepRun is what they share
@@ -260,7 +220,6 @@ struct Engine {
     // until that call has returned.  Off: every patch is applied at the call, stream-ordered, like a single planner's.
     struct DeferredPatch { int m, x, y, w, h; const uint8_t *ptr; };
     std::vector<DeferredPatch> deferred;
-    bool defer_patches = false;
     int flush_deferred();            // everything that is being held or deferred, applied
     int flush_deferred_only();
     // Held -- a small patch of a SINGLE planner handed over from HOST memory (ufm_patch_map) is not uploaded and applied at the call: its
@@ -275,7 +234,6 @@ struct Engine {
     PinArray<uint8_t> h_lazy;        // LAZY_SLOTS x 4096 bytes, pinned + mapped
     int lazy_next = 0;               // slot after the last one handed out
     bool lazy_dirty[LAZY_SLOTS] = {false, false, false, false};   // a kernel queued on the stream may still read the slot
-    bool lazy_patches = true;
     int hold_host_patch(const PatchRect &r, const uint8_t *host_patch);
     int flush_lazy();
     // C-space inflation (ufm_set_cspace; ufm_cspace.h).  Off -- the default, and a 1 x 1 mask -- nothing below exists
@@ -289,7 +247,7 @@ struct Engine {
     // holds, per map, how many cells of P.cost have each value, exactly, between any two calls: built after the raster is final
     // (engine_new_raster), corrected in front of every patch kernel.  After every build or patch the smallest and largest value present
     // are published to h_cen; "auto_multiplier" makes a step take that minimum as its heuristic multiplier.
-    bool census_on = false, auto_multiplier = false;
+    bool census_on = false;
     DevArray<uint32_t> d_census;     // [nmaps][256]
     struct CensusRange { int v[2]; };
     Published<CensusRange> h_cen;    // {min, max} over the engine's maps, and the sequence number of that copy
