@@ -1,4 +1,4 @@
-"""Diagnostic (GPU box, -DUFM_TIMING build: build/exp/libufm_timing.so or lib=path): how long after the last tile visit does the resident plan
+"""Diagnostic (GPU box, -DUFM_TIMING build: unige-tasi-path-planners_amd/libufm_timing.so, which make builds, or lib=path): how long after the last tile visit does the resident plan
 kernel end (workgroup 0's end-of-phase collect, ufm_relax.h), and what happened around the tiles at the start corner in the last microseconds --
 activations, visits (which workgroup, how many sweeps), in-visit refreshes.  FD-1 full plan.
 usage: end_of_phase.py size seed reps [lib=path] [events=1] [name=value ...]   (events=1: the event list of every run, not only the last)"""
@@ -8,7 +8,7 @@ sys.path.insert(0, ROOT)
 import numpy as np, ufm_amd
 size, seed, reps = int(sys.argv[1]), int(sys.argv[2]), int(sys.argv[3])
 kv = dict(a.split("=", 1) for a in sys.argv[4:])
-ufm_amd.use_library(os.path.join(ROOT, kv.pop("lib", "build/exp/libufm_timing.so")))
+ufm_amd.use_library(os.path.join(ROOT, kv.pop("lib", "unige-tasi-path-planners_amd/libufm_timing.so")))
 events = kv.pop("events", "0") != "0"
 L = ufm_amd.load_library()
 L.ufm_debug_plog.argtypes = [C.c_void_p, C.c_int]

@@ -1,12 +1,12 @@
-"""Diagnostic (GPU box, -DUFM_SWEEPSTAT build): what the patch sweeps of a plan find -- how many change nothing, how many node
-values change per sweep, how long the bursts are.  usage: sweep_stats.py lib=build/exp/libufm_sstat.so [size] [algo] [name=value ...]"""
+"""Diagnostic (GPU box, -DUFM_SWEEPSTAT build: unige-tasi-path-planners_amd/libufm_sstat.so, which make builds): what the patch sweeps of a plan find -- how many change nothing, how many node
+values change per sweep, how long the bursts are.  usage: sweep_stats.py [lib=unige-tasi-path-planners_amd/libufm_sstat.so] [size] [algo] [name=value ...]"""
 import ctypes as C, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np, ufm_amd
 pos = [a for a in sys.argv[1:] if "=" not in a]
 kv = dict(a.split("=", 1) for a in sys.argv[1:] if "=" in a)
-ufm_amd.use_library(os.path.join(ROOT, kv.pop("lib")))
+ufm_amd.use_library(os.path.join(ROOT, kv.pop("lib", "unige-tasi-path-planners_amd/libufm_sstat.so")))
 size = int(pos[0]) if pos else 4096
 algo = pos[1] if len(pos) > 1 else "FD"
 A = {"FD": ufm_amd.ALGO_FD, "SG": ufm_amd.ALGO_SG, "DFM": ufm_amd.ALGO_DFM}[algo]

@@ -1,5 +1,5 @@
-"""Diagnostic: where a tile visit spends its time (needs a libufm built with -DUFM_TIMING,
-UFM_LIB=build/libufm_timing.so).  Headline workload: FD-1, 4096^2 plan (+ optional replans)."""
+"""Diagnostic: where a tile visit spends its time (a library built with -DUFM_TIMING: --lib, by default
+unige-tasi-path-planners_amd/libufm_timing.so, which make builds).  Headline workload: FD-1, 4096^2 plan (+ optional replans)."""
 import argparse
 import ctypes as C
 import sys
@@ -15,7 +15,9 @@ ap.add_argument("--size", type=int, default=4096)
 ap.add_argument("--algo", default="FD")
 ap.add_argument("--replans", type=int, default=0)
 ap.add_argument("--param", action="append", default=[], help="name=value for ufm_set_param")
+ap.add_argument("--lib", default="unige-tasi-path-planners_amd/libufm_timing.so")
 a = ap.parse_args()
+ufm_amd.use_library(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), a.lib))
 algo = {"FD": (ufm_amd.ALGO_FD, 1), "SG": (ufm_amd.ALGO_SG, 2), "DFM": (ufm_amd.ALGO_DFM, 1)}[a.algo]
 L = ufm_amd.load_library()
 L.ufm_debug_tdiag.argtypes = [C.c_void_p, C.c_int]

@@ -1,7 +1,7 @@
 """Diagnostic (GPU box, -DUFM_TIMING build): visits per tile of the resident plan kernel against the tile's mean traversal cost.
 Premise to check (round 4): the ordering band is one width in VALUE units (2.5 tile crossings at the map's mean cost), i.e. tens of tiles deep
 where the terrain is cheap and about one tile deep where it is expensive -- so the repeat visits should be concentrated in the cheap tiles.
-usage: visits_by_cost.py [size] [seed] [lib=build/exp/libufm_timing.so] [name=value ...]"""
+usage: visits_by_cost.py [size] [seed] [lib=unige-tasi-path-planners_amd/libufm_timing.so] [name=value ...]"""
 import ctypes as C, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -10,7 +10,7 @@ pos = [a for a in sys.argv[1:] if "=" not in a]
 kv = dict(a.split("=", 1) for a in sys.argv[1:] if "=" in a)
 size = int(pos[0]) if pos else 4096
 seed = int(pos[1]) if len(pos) > 1 else 7
-ufm_amd.use_library(os.path.join(ROOT, kv.pop("lib", "build/exp/libufm_timing.so")))
+ufm_amd.use_library(os.path.join(ROOT, kv.pop("lib", "unige-tasi-path-planners_amd/libufm_timing.so")))
 L = ufm_amd.load_library()
 L.ufm_debug_tiles.argtypes = [C.c_void_p, C.c_int]
 cost = ufm_amd.synth.cost_map(seed, size, size)

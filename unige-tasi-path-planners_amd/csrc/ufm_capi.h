@@ -122,6 +122,10 @@ extern "C" {
 int ufm_tile_edge(void) { return T; }
 #ifdef UFM_STRICT_FENCES
 const char *ufm_version(void) { return "ufm-gfx950 0.1 (block-FIM, strict-fence checking build)"; }
+#elif defined(UFM_TIMING)
+const char *ufm_version(void) { return "ufm-gfx950 0.1 (block-FIM, timing build)"; }
+#elif defined(UFM_SWEEPSTAT)
+const char *ufm_version(void) { return "ufm-gfx950 0.1 (block-FIM, sweep-statistics build)"; }
 #else
 const char *ufm_version(void) { return T == 32 ? "ufm-gfx950 0.1 (block-FIM, tile 32)" : "ufm-gfx950 0.1 (block-FIM, tile 16)"; }
 #endif

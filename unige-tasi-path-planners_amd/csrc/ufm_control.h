@@ -155,14 +155,7 @@ __device__ void unpark(const DevParams &P, int qz, int k, float rbound, int &s_k
 // The resident lowering kernel stands in for launch k of the lowering queue and everything after it: this kernel hands
 // it the entries of list k % 3 and does the list bookkeeping a launch does for its successors (k_relax, block 0) ...
 __global__ void k_own_import(DevParams P, int k) {
-#ifdef UFM_TIMING
-    if (blockIdx.x == 0 && threadIdx.x == 0) g_tile_t0 = wall_clock64();
-    for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < TILE_DIAG_MAX; t += gridDim.x * blockDim.x) {
-        g_tile[0][t] = 0xFFFFFFFFu; g_tile[1][t] = 0u; g_tile[2][t] = 0xFFFFFFFFu; g_tile[3][t] = 0u; g_tile[4][t] = 0u;
-        g_push64[t] = ~0ull;
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) { g_nvis = 0u; g_nplog = 0u; }
-#endif
+    diag_phase_begin();
     const int r = k % 3, rz = (k + 2) % 3;
     const int n = P.ctr->cnt[Q_LOWER][r];
     const int *cand = P.cand + (size_t)(Q_LOWER * 3 + r) * P.NT;

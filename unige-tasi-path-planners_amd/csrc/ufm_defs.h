@@ -1,4 +1,4 @@
-// ufm_defs.h -- build switches and tuned constants, the HBM layout (DevParams), the tile queues of the launch chain and of the resident kernel, diagnostics
+// ufm_defs.h -- build switches and tuned constants, the HBM layout (DevParams), the tile queues of the launch chain and of the resident kernel
 // (a piece of ufm_engine.hip, the engine's one translation unit: included there, inside its anonymous namespace)
 #pragma once
 
@@ -6,8 +6,10 @@
 //   UFM_TILE            tile edge, 16 (default) or 32
 //   UFM_STRICT_FENCES   the checking build of the resident kernel's memory protocol (libufm_strict.so)
 //   UFM_REGION_NG0      tiles in the LDS copy of the block replan kernel's write-back (libufm_strict.so: 2)
-//   UFM_TIMING          in-kernel timing and traces (diagnostic builds of tools/)
-//   UFM_SWEEPSTAT       what the patch sweeps find (diagnostic build of tools/sweep_stats.py)
+//   UFM_TIMING          in-kernel timing and traces (libufm_timing.so: the diagnostic build of tools/front_timing.py, visit_timing.py, end_of_phase.py, visits_by_cost.py)
+//   UFM_SWEEPSTAT       what the patch sweeps find (libufm_sstat.so: the diagnostic build of tools/sweep_stats.py)
+// The last two only fill the hooks of ufm_diag.h, which are empty functions otherwise: the kernels' own text tests neither, and
+// tests/test_gpu_diag_builds.py holds both builds to the product's fields.
 // Every other UFM_* name is a tuned constant: a constexpr next to the measurement that chose its value.  Variants that were measured
 // and not kept are in DESIGN.md section 11 and, where they were more than a line, as patches under tools/experiments/.
 #ifndef UFM_TILE
@@ -300,29 +302,6 @@ __device__ __forceinline__ int own_tile(const DevParams &P, int o, int s, int &m
     tx = bx * 16 + (o >> P.own_ys); ty = (by << P.own_ys) + (o & ((1 << P.own_ys) - 1));
     return (tx < P.TX && ty < P.TY) ? m * P.NTm + tx * P.TY + ty : -1;
 }
-#ifdef UFM_TIMING
-// per tile (resident kernel): [0] first visit start, [1] end of the last visit that changed a value, [2] earliest activation not yet
-// taken, [3] visits, [4] sum of activation -> visit start waits; 100 MHz ticks since the launch's first visit (g_tile_t0)
-constexpr int TILE_DIAG_MAX = 1 << 19;
-__device__ unsigned int g_tile[5][TILE_DIAG_MAX];
-__device__ unsigned long long g_tile_t0;
-__device__ unsigned long long g_sdiag[16];   // looks of idle workgroups: [0] looks, [1] with nothing to take, [2] helping attempts, [3] a victim's word found,
-                                             // [4] inside the band, [5] taken, [6] takes ahead that failed, [7] fresh takes that failed
-// ... and the visits themselves, for the critical path: {tile, start, end, earliest activation taken: time, tile that sent it}
-constexpr int VIS_DIAG_MAX = 1 << 20;
-__device__ unsigned long long g_push64[TILE_DIAG_MAX];     // per tile: {time, sender} of the earliest activation not yet taken
-__device__ unsigned int g_vis[VIS_DIAG_MAX][5];
-__device__ unsigned int g_nvis;
-// events around the corner tiles (0..1, 0..1) of map 0: {time, a, b, c}; b = 0xFFFFFFFF: workgroup 0 saw the end; 0xFFFFFFFE: in-visit refresh
-// (a = tile, c = what the exchange returned); 0xFFFFFFFD: a look of the owner (a = workgroup, c = its best priority); else an activation a -> b with priority c
-constexpr int PLOG_MAX = 1 << 14;
-__device__ unsigned int g_plog[PLOG_MAX][4];
-__device__ unsigned int g_nplog;
-__device__ __forceinline__ void plog(unsigned int a, unsigned int b, unsigned int c) {
-    const unsigned int i = atomicAdd(&g_nplog, 1u);
-    if (i < PLOG_MAX) { g_plog[i][0] = (unsigned int)(wall_clock64() - g_tile_t0); g_plog[i][1] = a; g_plog[i][2] = b; g_plog[i][3] = c; }
-}
-#endif
 // -DUFM_STRICT_FENCES (a checking build, libufm_strict.so: tests/test_strict_fences.py holds the product build to it bit for bit): the
 // textbook form of the protocol -- an agent-scope release fence in front of every activation and of every lock release, an agent-scope
 // acquire fence behind every take -- next to the product's argued one (sc1 stores and loads, s_waitcnt vmcnt(0), relaxed atomics; the table
@@ -340,14 +319,7 @@ __device__ __forceinline__ void own_push(const DevParams &P, int gt, int pbits, 
     UFM_STRICT_RELEASE();
     __hip_atomic_fetch_min(&P.own_prio[(size_t)o * P.own_slots + s], pbits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __hip_atomic_fetch_min(&P.own_min[o], pbits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#ifdef UFM_TIMING
-    if (gt < TILE_DIAG_MAX) {
-        const unsigned int now = (unsigned int)(wall_clock64() - g_tile_t0);
-        atomicMin(&g_tile[2][gt], now);
-        atomicMin(&g_push64[gt], ((unsigned long long)now << 32) | (unsigned int)from);
-        if (gt / P.TY < 2 && gt % P.TY < 2) plog((unsigned int)from, (unsigned int)gt, (unsigned int)pbits);
-    }
-#endif
+    diag_pushed(gt, from, pbits, P.TY);
 }
 // Values other workgroups write while the resident kernel runs are read and written past the per-XCD L2
 // (agent-scope accesses); the launch-per-band-step kernels rely on the kernel boundaries instead.
@@ -362,34 +334,3 @@ template <bool COH> __device__ __forceinline__ void st_f(float *p, float v) {
     if constexpr (COH) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     else *p = v;
 }
-
-// ---- optional in-kernel timing of tile visits (-DUFM_TIMING, diagnostic builds only) -------
-// g_tdiag: [0] sum of pop->staged, [1] sum of sweep phases, [2] sum of write-back/activation,
-// [3] visits, [4] sum of per-block busy time, [5] blocks, [8..39] histogram of visit times (2 us bins)
-// all in 10 ns ticks of the constant 100 MHz counter
-#ifdef UFM_TIMING
-__device__ unsigned long long g_tdiag[64];
-// trace of the lowering launches UFM_TRACE_K0 .. +7: per record {launch | block<<16 | kind<<40, t0, t1, sweeps};
-// kind 0 = tile visit (pop .. end), 1 = block lifetime (entry .. exit)
-constexpr int UFM_TRACE_K0 = 300;
-__device__ unsigned long long g_trace[4 * 16384];
-__device__ unsigned int g_ntrace;
-// per-wave timeline of ONE tile visit (the first long-list visit of workgroup 0 in launch UFM_TRACE_K0):
-// records {type, t, value}; 1 burst start (wake bits), 2 burst end (sweeps in it), 3 idle, 4 woken, 5 vote
-__device__ unsigned long long g_wtrace[16 * 256 * 2];
-__device__ unsigned int g_nw[16];
-#define UFM_WREC(type, val) do { if (wtrace_on && lane == 0) { const unsigned int i_ = g_nw[w]++; if (i_ < 256) { \
-    g_wtrace[(w * 256 + i_) * 2] = ((unsigned long long)(type) << 32) | (unsigned int)(val); g_wtrace[(w * 256 + i_) * 2 + 1] = wall_clock64(); } } } while (0)
-__device__ __forceinline__ void trace_rec(int k, int kind, unsigned long long t0, unsigned long long t1, long long sw) {
-    if (k < UFM_TRACE_K0 || k >= UFM_TRACE_K0 + 8) return;
-    const unsigned int i = atomicAdd(&g_ntrace, 1u);
-    if (i >= 16384) return;
-    g_trace[4 * i] = (unsigned long long)k | ((unsigned long long)blockIdx.x << 16) | ((unsigned long long)kind << 40);
-    g_trace[4 * i + 1] = t0; g_trace[4 * i + 2] = t1; g_trace[4 * i + 3] = (unsigned long long)sw;
-}
-#define UFM_TICK(v) const unsigned long long v = wall_clock64()
-#else
-#define UFM_TICK(v)
-#define UFM_WREC(type, val)
-#endif
-

@@ -2,11 +2,6 @@
 // (a piece of ufm_engine.hip, the engine's one translation unit: included there, inside its anonymous namespace)
 #pragma once
 
-#ifdef UFM_SWEEPSTAT
-// diagnostics (-DUFM_SWEEPSTAT, tools/sweep_stats.py): what the patch sweeps of k_relax find.  [0] sweeps, [1] sweeps that changed no node,
-// [2] node values changed, [3] bursts, [4] bursts whose first sweep changed nothing, [5] node values lowered, [8..23] histogram of sweeps per burst (1..16)
-__device__ unsigned long long g_sstat[32];
-#endif
 // ---- update operators -------------------------------------------------------
 // Correctly rounded fp32 square root (std::sqrt of the reference, Macros.h:12):
 // v_sqrt_f32 is good to 1 ulp; two fused residuals pick the neighbour that is

@@ -1,5 +1,8 @@
 // ufm_relax.h -- k_relax (one tile visit: staging, asynchronous in-LDS sweeps, write-back and activations) in its three scheduler forms -- fused triage over a short list (!DYN), cursor hand-out of a ready list (DYN, with k_triage), resident owners (OWNK) --, and k_triage
 // (a piece of ufm_engine.hip, the engine's one translation unit: included there, inside its anonymous namespace)
+// The kernel body is the algorithm alone.  What the diagnostic builds record about it goes through the hooks of ufm_diag.h -- dv.begin / staged /
+// swept / end and dv.wave_rec around a visit, diag_count, diag_look, diag_sweep, diag_burst, diag_rank ... --, which are empty functions in the
+// product: no preprocessor conditional is left in k_relax, its two .inc files or k_triage.
 #pragma once
 
 // ---- the hot kernel ------------------------------------------------------------------------
@@ -59,9 +62,6 @@ __global__ __launch_bounds__(OWNK == 2 ? NTHR / 2 : NTHR, UFM_RELAX_WAVES) void 
     constexpr bool EARLY = OWNK == 1 && !is_dfm<ALGO>;
     __shared__ float Os[EARLY ? TT : 1];
     __shared__ int s_emin[EARLY ? 16 * 9 : 1];
-#ifdef UFM_TIMING
-    __shared__ unsigned int s_misc_vi;
-#endif
     __shared__ uint8_t Bs[BPRAISE ? TT : 1];   // the tile's back-pointer bytes (invalidation of the node planners, and of MS-DFM level 1 when it follows them)
     __shared__ int s_qw[2];       // in-visit refresh: [0] this tile's queue word as an idle wave last saw it (loaded straight into LDS), [1] refreshes of this visit
 
@@ -88,7 +88,8 @@ __global__ __launch_bounds__(OWNK == 2 ? NTHR / 2 : NTHR, UFM_RELAX_WAVES) void 
     }
     if (n == 0) return;
     const int focused = P.dyn->focused, thr = P.dyn->thr;
-    UFM_TICK(tkb);
+    DiagVisit dv;                 // (the timing build's stamps of the launch and of the visit in progress: ufm_diag.h; empty otherwise)
+    dv.launch_begin();
     const int *cand = P.cand + (size_t)(Q * 3 + r) * P.NT;
     constexpr int CROWS = is_dfm<ALGO> ? T : T + 1;
     constexpr int COFF = is_dfm<ALGO> ? 0 : 1;
@@ -263,9 +264,7 @@ __global__ __launch_bounds__(OWNK == 2 ? NTHR / 2 : NTHR, UFM_RELAX_WAVES) void 
                     // resident when the others had left (the device was shared) must not wait out a limit of its own
                     if (aborted == 2) stop = true;            // workgroup 0 has seen the end
                     else if (stop) __hip_atomic_store(&P.ctr->own_abort, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#ifdef UFM_TIMING
-                    if (blockIdx.x == 0) plog(stop ? 1u : 0u, stop ? 0xFFFFFFFFu : 0xFFFFFFFDu, (unsigned int)(b >> 32));
-#endif
+                    diag_look(stop, (unsigned int)(b >> 32));
                     const bool late = !stop && (aborted || wall_clock64() - own_t0 > P.own_limit);
                     if (late) { atomicAdd(&P.ctr->own_stops, 1); __hip_atomic_store(&P.ctr->own_abort, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
                     const bool taking = take && !stop && !late;
@@ -276,11 +275,9 @@ __global__ __launch_bounds__(OWNK == 2 ? NTHR / 2 : NTHR, UFM_RELAX_WAVES) void 
                     int pr = (int)(b >> 32);
                     const bool got = taking && own_take_resolve(own_base + (int)(unsigned int)b, pr, r_old, r_lk);
                     s_own[3] = got ? pr : INFBITS;
-#ifdef UFM_TIMING
-                    atomicAdd(&g_sdiag[0], 1ull);
-                    if (!taking) atomicAdd(&g_sdiag[1], 1ull);
-                    if (taking && !got) atomicAdd(&g_sdiag[7], 1ull);
-#endif
+                    diag_count(SDIAG_LOOKS, true);
+                    diag_count(SDIAG_LOOKS_EMPTY, !taking);
+                    diag_count(SDIAG_FRESH_FAILED, taking && !got);
                     if (stop || late) flag = -1;
                     else if (got) flag = 1;
                     s_gmin = flag;
@@ -314,25 +311,10 @@ __global__ __launch_bounds__(OWNK == 2 ? NTHR / 2 : NTHR, UFM_RELAX_WAVES) void 
         }
         first_pop = false;
         if (i >= n) {
-#ifdef UFM_TIMING
-            if (MODE == MODE_LOWER && tid == 0) trace_rec(k, 1, tkb, wall_clock64(), 0);
-#endif
+            dv.launch_end(MODE == MODE_LOWER && tid == 0, k);
             break;
         }
-        UFM_TICK(tk0);
-#ifdef UFM_TIMING
-        if (OWN && tid == 0 && gt_own >= 0 && gt_own < TILE_DIAG_MAX) {
-            const unsigned int now = (unsigned int)(tk0 - g_tile_t0);
-            atomicMin(&g_tile[0][gt_own], now);
-            const unsigned int pushed = atomicExch(&g_tile[2][gt_own], 0xFFFFFFFFu);
-            if (pushed != 0xFFFFFFFFu && now > pushed) atomicAdd(&g_tile[4][gt_own], now - pushed);
-            atomicAdd(&g_tile[3][gt_own], 1u);
-            const unsigned long long p64 = atomicExch(&g_push64[gt_own], ~0ull);
-            const unsigned int vi = atomicAdd(&g_nvis, 1u);
-            s_misc_vi = vi;
-            if (vi < VIS_DIAG_MAX) { g_vis[vi][0] = gt_own; g_vis[vi][1] = now; g_vis[vi][2] = 0u; g_vis[vi][3] = (unsigned int)(p64 >> 32); g_vis[vi][4] = (unsigned int)p64; }
-        }
-#endif
+        dv.begin(OWN && tid == 0, gt_own);
         const int gt = OWN ? gt_own : (DYN ? (i < n_long ? (i == (int)blockIdx.x ? spec_first : P.ready[i]) : P.ready[P.NT - 1 - (i - n_long)]) : cand[i]);
         const int pbits = (DYN || OWN) ? 0 : prio_read(P, Q, k, gt);
         const int m = gt / P.NTm, t = gt - m * P.NTm;
@@ -429,20 +411,13 @@ __global__ __launch_bounds__(OWNK == 2 ? NTHR / 2 : NTHR, UFM_RELAX_WAVES) void 
         }
         if constexpr (EARLY) { if (io_on) Os[tid] = gl0; if (tid < NWV * 9) s_emin[tid] = INFBITS; if (tid == 0) { s_qw[0] = OWN_MARK; s_qw[1] = own_parked ? 0x20000 : 0; } }
         __syncthreads();
-        UFM_TICK(tk1);
-#ifdef UFM_TIMING
-        const int dbg_hint = P.hint[gt];
-        const int dbg_rank = P.rank[gt];
-        const int dbg_ninf0 = __syncthreads_count(io_on && gl0 == INFINITY);
-#endif
+        dv.staged(P.hint, P.rank, gt, io_on, gl0);
         // One changed element (r, c) of the tile goes out: its value (was `gref` in HBM) into the tile's own record and into the rings
         // of the neighbours it borders; bm[9] (LDS, float bits, one entry per direction, 4 = this tile itself) notes the smallest changed
         // value each neighbour has to hear of.  Used by the write-back at the end of a visit and by the early hand-off during it.
         auto wb_store = [&](int wb_r, int wb_c, float gf) {
             st_f<OWN>(&Gt[wb_r * T + wb_c], gf);
-#ifdef UFM_TIMING
-            s_qw[1] |= 0x10000;      // (diagnostics: the visit changed a value)
-#endif
+            diag_value_changed(&s_qw[1]);
             {   // a border value also lives in the rings of the neighbours it borders
                 const int er_ = (wb_r == 0) ? -1 : ((wb_r == T - 1) ? 1 : 0);
                 const int ec_ = (wb_c == 0) ? -1 : ((wb_c == T - 1) ? 1 : 0);
@@ -602,17 +577,15 @@ __global__ __launch_bounds__(OWNK == 2 ? NTHR / 2 : NTHR, UFM_RELAX_WAVES) void 
 #include "ufm_relax_early.inc"
         const bool lax = is_dfm<ALGO> && s_misc[1] > UFM_DFM1_LAX_VISITS;
         bool conv = false;
-#ifdef UFM_TIMING
-        const bool wtrace_on = DYN && MODE == MODE_LOWER && k == UFM_TRACE_K0 && i == 0;
-        UFM_WREC(0, s_misc[1]);
-#endif
+        dv.sweeps_begin(DYN && MODE == MODE_LOWER && i == 0, k);
+        dv.wave_rec(WREC_VISIT, s_misc[1]);
         for (;;) {
             int bits = 0;
             if (lane == 0) bits = atomicExch(&s_wake[wp], 0);
             bits = __builtin_amdgcn_readfirstlane(bits);
             bool vote = __hip_atomic_load(&s_giveup, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != 0;
             if (bits && !vote) {
-                UFM_WREC(1, bits);
+                dv.wave_rec(WREC_BURST, bits);
 #pragma unroll
                 for (int j = 0; j < PPWK; ++j) {
                     if (!(bits & (1 << j))) continue;    // wave-uniform
@@ -623,9 +596,7 @@ __global__ __launch_bounds__(OWNK == 2 ? NTHR / 2 : NTHR, UFM_RELAX_WAVES) void 
                     // re-reading it from LDS after the evaluation only put a second LDS round trip on the
                     // dependent chain of every sweep
                     float g = ctr[0];
-#ifdef UFM_SWEEPSTAT
-                    const int sst_c0 = cnt[j];
-#endif
+                    const int burst_c0 = cnt[j];     // (for diag_burst: the sweeps of this burst)
                     for (int b = 0; b < 16 && again; ++b) {
                         asm volatile("" ::: "memory");   // re-read the LDS tile every sweep (other waves and lanes write it)
                         float rl;                        // this lane's candidate
@@ -659,18 +630,7 @@ __global__ __launch_bounds__(OWNK == 2 ? NTHR / 2 : NTHR, UFM_RELAX_WAVES) void 
                         if (MODE == MODE_RAISE) wanted = mask;
                         else if (is_dfm<ALGO>) wanted = __builtin_amdgcn_ballot_w64(want);
                         else wanted = __builtin_amdgcn_fcmpf(nv, g, 14);   // lanes with nv != g (14 = FCMP_UNE), as a v_cmp into an SGPR pair
-#ifdef UFM_SWEEPSTAT
-                        {
-                            const unsigned long long chg = __builtin_amdgcn_ballot_w64(gn != g), low = __builtin_amdgcn_ballot_w64(gn < g);
-                            if (lane == 0) {
-                                atomicAdd(&g_sstat[0], 1ull);
-                                if (!chg) atomicAdd(&g_sstat[1], 1ull);
-                                atomicAdd(&g_sstat[2], (unsigned long long)__popcll(chg) / 4ull);
-                                atomicAdd(&g_sstat[5], (unsigned long long)__popcll(low) / 4ull);
-                                if (b == 0) { atomicAdd(&g_sstat[3], 1ull); if (!chg) atomicAdd(&g_sstat[4], 1ull); }
-                            }
-                        }
-#endif
+                        diag_sweep(gn != g, gn < g, b == 0);
                         g = gn;
                         UFM_SWEEP_FENCE();                               // value before wake bit
                         if ((mask & wake_sel) != 0ull && wbit[j] && lane != 4)
@@ -679,9 +639,7 @@ __global__ __launch_bounds__(OWNK == 2 ? NTHR / 2 : NTHR, UFM_RELAX_WAVES) void 
                         ++tot;
                         again = wanted != 0ull;
                     }
-#ifdef UFM_SWEEPSTAT
-                    if (lane == 0) atomicAdd(&g_sstat[8 + min(cnt[j] - sst_c0, 16) - 1], 1ull);
-#endif
+                    diag_burst(cnt[j] - burst_c0);
                     if (again && lane == 0)              // burst cap: leave the rest to the next take
                         __hip_atomic_fetch_or(&s_wake[wp], 1 << j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                     if constexpr (EARLY) if (!(P.own_flags & 2)) {
@@ -718,7 +676,7 @@ __global__ __launch_bounds__(OWNK == 2 ? NTHR / 2 : NTHR, UFM_RELAX_WAVES) void 
                         }
                     }
                 }
-                UFM_WREC(2, tot);
+                dv.wave_rec(WREC_BURST_END, tot);
                 if (tot >= PPWK * max_sweeps && lane == 0)  // give up this visit; the tile is re-queued
                     __hip_atomic_store(&s_giveup, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 continue;
@@ -726,7 +684,7 @@ __global__ __launch_bounds__(OWNK == 2 ? NTHR / 2 : NTHR, UFM_RELAX_WAVES) void 
             if (!vote) {                                 // nothing to do: idle until woken or all idle
                 if (bits && lane == 0) __hip_atomic_fetch_or(&s_wake[wp], bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 if (lane == 0) atomicAdd(&s_idle, 1);
-                UFM_WREC(3, 0);
+                dv.wave_rec(WREC_IDLE, 0);
                 int polls = 0;
                 if constexpr (NWV == 8) UFM_SETPRIO(0);         // (an idle wave's looks: behind the waves that sweep)
                 for (;;) {
@@ -746,7 +704,7 @@ __global__ __launch_bounds__(OWNK == 2 ? NTHR / 2 : NTHR, UFM_RELAX_WAVES) void 
                         __hip_atomic_load(&s_giveup, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != 0) { vote = true; break; }
                     if (__hip_atomic_load(&s_wake[wp], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != 0) {
                         if (lane == 0) atomicSub(&s_idle, 1);
-                        UFM_WREC(4, 0);
+                        dv.wave_rec(WREC_WOKEN, 0);
                         break;
                     }
                 }
@@ -756,7 +714,7 @@ __global__ __launch_bounds__(OWNK == 2 ? NTHR / 2 : NTHR, UFM_RELAX_WAVES) void 
                 __hip_atomic_fetch_or(&s_wake[wp], bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   // put back what was taken
             }
             // vote: everybody arrives first, then the wake bits are stable
-            UFM_WREC(5, 0);
+            dv.wave_rec(WREC_VOTE, 0);
             __syncthreads();
             const int work = __syncthreads_or(__hip_atomic_load(&s_wake[wp], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != 0);
             const int gave_up = __hip_atomic_load(&s_giveup, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -766,7 +724,7 @@ __global__ __launch_bounds__(OWNK == 2 ? NTHR / 2 : NTHR, UFM_RELAX_WAVES) void 
         }
         if (lane == 0 && tot) { atomicAdd(&s_misc[2], tot); atomicMax(&s_misc[3], tot); }
         __syncthreads();
-        UFM_TICK(tk2);
+        dv.swept();
 
         int own_ro = INFBITS, own_rl = 1;     // thread 0: what the two atomics of the take ahead returned (looked at after the write-back)
         if constexpr (OWN) {
@@ -805,9 +763,7 @@ __global__ __launch_bounds__(OWNK == 2 ? NTHR / 2 : NTHR, UFM_RELAX_WAVES) void 
             if (tid == 0) {
                 int pr = (int)(s_best >> 32);                    // (own_decide's choice: nobody has touched s_best since)
                 s_own[3] = (own_next >= 0 && own_take_resolve(own_next, pr, own_ro, own_rl)) ? pr : INFBITS;
-#ifdef UFM_TIMING
-                if (own_next >= 0 && s_own[3] >= INFBITS) atomicAdd(&g_sdiag[6], 1ull);
-#endif
+                diag_count(SDIAG_AHEAD_FAILED, own_next >= 0 && s_own[3] >= INFBITS);
             }
         }
         __syncthreads();
@@ -836,24 +792,7 @@ __global__ __launch_bounds__(OWNK == 2 ? NTHR / 2 : NTHR, UFM_RELAX_WAVES) void 
             }
         }
         if constexpr (OWN) prev_gt = gt;
-#ifdef UFM_TIMING
-        if (MODE == MODE_LOWER) {
-            const int dbg_ninf1 = __syncthreads_count(io_on && gf == INFINITY);
-            if (tid == 0) {
-                const unsigned long long tk3 = wall_clock64();
-                if (OWN && gt < TILE_DIAG_MAX && (!EARLY || (s_qw[1] & 0x10000))) g_tile[1][gt] = (unsigned int)(tk3 - g_tile_t0);
-                if (OWN && s_misc_vi < VIS_DIAG_MAX) g_vis[s_misc_vi][2] = (unsigned int)(tk3 - g_tile_t0);
-                if (OWN && gt / P.TY < 2 && gt % P.TY < 2) plog((unsigned int)gt, 0xFFFFFFFBu, (conv ? 1u : 0u) | ((unsigned int)s_misc[3] << 8) | ((unsigned int)blockIdx.x << 20));
-                if (EARLY) atomicAdd(&g_tdiag[6], (unsigned long long)(s_qw[1] & 0xFFFF));   // in-visit refreshes
-                atomicAdd(&g_tdiag[0], tk1 - tk0); atomicAdd(&g_tdiag[1], tk2 - tk1); atomicAdd(&g_tdiag[2], tk3 - tk2);
-                atomicAdd(&g_tdiag[3], 1ull);
-                const unsigned long long bin = (tk3 - tk0) / 200;
-                atomicAdd(&g_tdiag[8 + (bin < 31 ? bin : 31)], 1ull);
-                atomicAdd(&g_tdiag[40 + (s_misc[3] < 23 ? s_misc[3] : 23)], 1ull);   // histogram of per-wave sweep counts / 1
-                trace_rec(k, 0, tk0, tk3, (long long)(s_misc[3] & 255) | ((long long)min(s_misc[1], 255) << 8) | ((long long)min(dbg_hint, 255) << 16) | ((long long)dbg_ninf0 << 24) | ((long long)dbg_ninf1 << 40) | ((long long)dbg_rank << 52));
-            }
-        }
-#endif
+        dv.end(MODE == MODE_LOWER, OWN, EARLY, k, gt, P.TY, conv, s_misc, s_qw, io_on, gf);
     }
     if (tid == 4 && s_stat[0]) {
         atomicMax(&P.lmax[k & (LMAX - 1)], st_lmax);
@@ -904,12 +843,7 @@ __global__ void k_triage(DevParams P, int k, float delta, float rbound) {
         // a launch lasts (work per CU) + (its longest visit) when long visits are handed out last;
         // tiles a front is still crossing (first visit of the step, or many sweeps last time) go first
         const bool lng = release && (P.touched[gt] == 0 || P.hint[gt] >= UFM_LONG_SWEEPS);
-#ifdef UFM_TIMING
-        if (release && MODE == MODE_LOWER) {
-            const float lo = __int_as_float(P.ctr->lmin[Q][r]);
-            P.rank[gt] = (int)fminf(255.0f, fmaxf(0.0f, 255.0f * (__int_as_float(pbits) - lo) / fmaxf(delta, 1e-6f)));
-        }
-#endif
+        diag_rank(release && MODE == MODE_LOWER, P.rank, gt, pbits, &P.ctr->lmin[Q][r], delta);
         // What an entry becomes -- released (long / short), parked, carried -- is decided above; the words that say whether
         // a park / carry is the tile's first are swapped next, all of them in flight together; then the four list cursors
         // are advanced by ONE instruction (lanes 0..3, one cursor each, the counts from ballots) instead of four returning

@@ -34,17 +34,13 @@
             if (lane == 0) mine = atomicCAS(&s_qw[0], seen, OWN_MARK) == seen;
             if (!__builtin_amdgcn_readfirstlane(mine)) return false;
             if (lane == 0) { atomicSub(&s_idle, 1); s_qw[1] += 1; }
-#ifdef UFM_TIMING
-            if (lane == 0 && gt < TILE_DIAG_MAX) atomicExch(&g_tile[2][gt], 0xFFFFFFFFu);
-#endif
+            diag_refresh_claimed(gt);
             int was = OWN_MARK;
             if (lane == 0) was = __hip_atomic_exchange(&P.own_prio[own_slot_now], OWN_MARK + (int)blockIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             was = __builtin_amdgcn_readfirstlane(was);
             UFM_STRICT_ACQUIRE();
-#ifdef UFM_TIMING
-            if (lane == 0 && gt / P.TY < 2 && gt % P.TY < 2) plog((unsigned int)gt, 0xFFFFFFFEu, (unsigned int)was);
-#endif
+            diag_refresh_taken(gt, P.TY, was);
             if (was < INFBITS) {                 // (an activation: its values were stored before it was queued)
                 if (lane == 0) atomicMin(&s_emin[w * 9 + 4], was);   // (its priority counts for the tile's own, should the visit end at the sweep cap)
                 int t_ = tid;

@@ -87,9 +87,7 @@
         if (lane == 0 && hk != ~0ull) atomicMin(&s_best, hk);
         lds_barrier();
         const unsigned long long vk = s_best;
-#ifdef UFM_TIMING
-        if (tid == 0) atomicAdd(&g_sdiag[2], 1ull);
-#endif
+        diag_count(SDIAG_HELP_TRIES, tid == 0);
         if (vk == ~0ull) { lds_barrier(); return -1; }
         const float band_top = __int_as_float((int)(vk >> 32)) + delta;
         if (hint != INFBITS && !(__int_as_float(hint) > band_top)) {
@@ -115,22 +113,16 @@
         lds_barrier();
         if (tid == 0) {
             const unsigned long long b2 = s_best;
-#ifdef UFM_TIMING
-            if (b2 != ~0ull) atomicAdd(&g_sdiag[3], 1ull);
-#endif
+            diag_count(SDIAG_HELP_FOUND, b2 != ~0ull);
             if (b2 != ~0ull && !(__int_as_float((int)(b2 >> 32)) > band_top)) {
-#ifdef UFM_TIMING
-                atomicAdd(&g_sdiag[4], 1ull);
-#endif
+                diag_count(SDIAG_HELP_IN_BAND, true);
                 const int gw = s_bmin[((unsigned int)b2 >> 28) & 15u] * P.own_slots + (int)((unsigned int)b2 & 0x0FFFFFFFu);
                 int pr = (int)(b2 >> 32);
                 int r_old, r_lk;
                 own_take_issue(gw, pr, r_old, r_lk);
                 if (own_take_resolve(gw, pr, r_old, r_lk)) {
                     s_own[3] = pr; s_gmin = gw;
-#ifdef UFM_TIMING
-                    atomicAdd(&g_sdiag[5], 1ull);
-#endif
+                    diag_count(SDIAG_HELP_TAKEN, true);
                     __hip_atomic_fetch_min(&P.own_min[blockIdx.x], pr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // what this workgroup holds now
                 }
             }
