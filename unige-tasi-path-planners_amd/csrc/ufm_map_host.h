@@ -4,7 +4,7 @@
 // (a piece of ufm_engine.hip, the engine's one translation unit: included there behind ufm_host.h, inside its anonymous namespace)
 #pragma once
 
-constexpr PatchRouteConfig PATCH_ROUTE_CONFIG{PATCH_MULTI, 4096, 64, Engine::LAZY_SLOTS};
+constexpr PatchRouteConfig PATCH_ROUTE_CONFIG{PATCH_MULTI, 4096, REGION_HELD_EDGE, Engine::LAZY_SLOTS};   // (hold_edge: what the block kernel's divisions and change mask are made for, ufm_region_rect.h)
 
 // ---- what is held or deferred, applied -----------------------------------------------------------------------------------------
 int Engine::flush_deferred() {       // a single planner's host patches, then a batch's deferred device patches

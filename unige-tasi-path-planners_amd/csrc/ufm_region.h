@@ -24,15 +24,9 @@ constexpr int UFM_REGION_PRIO = 2;
 #define UFM_REGION_SETPRIO(x) __builtin_amdgcn_s_setprio(x)
 constexpr int UFM_REGION_IDLE_SLEEP = 8;         // an idle wave of the block kernel looks at its wake words this often (x 64 clocks): 1 / 4 / 16 / 32 / 64 -> 100 replans 18.9 / 18.0 / 17.6 / 17.6 / 17.8 ms (the looks of twelve idle waves take issue slots and LDS cycles from the four that sweep)
 constexpr int UFM_REGION_IDLE_SLEEP_RAISE = 8;   // ... in the node planners' invalidation phase, whose sweeps are a few loads and a compare
-constexpr int RTMAX = 128 / T;            // block edge in tiles (8 for 16 x 16 tiles: field 71 KB + cost bytes 17 KB + back-pointer codes 16 KB of the CU's 160 KB LDS)
-constexpr int RN = RTMAX * T;             // ... in elements (160)
-constexpr int RP = RN + 8;                // LDS pitch of the block's field: rows 4 apart on distinct banks (168 = 5*32 + 8)
-constexpr int RCP = RN + 4;               // pitch of the cost bytes
-constexpr int RBP = RN;                   // pitch of the back-pointer codes
-constexpr int TP = T / 4;                 // 4x4-element patches per tile side
-constexpr int RPW = RTMAX * TP / 4;       // patches per wave per side: patch (pr, pc) belongs to wave ((pr & 3) << 2 | (pc & 3))
-constexpr int RWW = (RPW * RPW + 31) / 32;   // wake words per wave
-constexpr int RFRAME = 4 * RTMAX + 4;     // tiles around the block
+// the block's geometry (RTMAX, RN, RP, RCP, RBP, TP, RPW, RWW, RFRAME) and every index rule of the kernel: plain C++, walked on the CPU by tests/cpp/region_rect_driver.cpp
+#include "ufm_region_rect.h"
+static_assert(REGION_T == T && REGION_UPT * 64 == TT, "ufm_region_rect.h takes the tile edge as ufm_defs.h does");
 
 struct RegionJob {
     ReplanBegin rb;                       // step bookkeeping, consumed patch rectangles, invalidation queue index, margin
@@ -152,20 +146,9 @@ __device__ void region_phase(const DevParams &P, const RegionJob &J, float *Gs, 
     const int tid = threadIdx.x, w = wave_index16(tid >> 6), lane = tid & 63;
     const int q = lane & 3, nd = lane >> 2;
     const int nprow = J.ntx * TP, npcol = J.nty * TP;
-    unsigned long long wake_sel = 0ull;
-    if (lane < 9) {
-        const int dr = lane / 3 - 1, dc = lane % 3 - 1;
-        wake_sel = ~0ull;
-        if (dr < 0) wake_sel &= 0x000000000000FFFFull; else if (dr > 0) wake_sel &= 0xFFFF000000000000ull;
-        if (dc < 0) wake_sel &= 0x000F000F000F000Full; else if (dc > 0) wake_sel &= 0xF000F000F000F000ull;
-    }
+    const unsigned long long wake_sel = region_wake_sel(lane);
     const int colour = ((nd >> 2) & 1) | ((nd & 1) << 1);
-    // a patch's 3 x 3 neighbours: patch (pr, pc) belongs to wave ((pr & 3) << 2) | (pc & 3) and is bit (pr >> 2) * RPW + (pc >> 2) of that wave's words; this
-    // wave's patches all have (pr & 3, pc & 3) = (w >> 2, w & 3), so the neighbour's wave and the distance of its bit from this patch's bit are per-lane constants
-    const bool wt_lane = lane < 9;
-    const int wt_dr = wt_lane ? lane / 3 - 1 : 0, wt_dc = wt_lane ? lane % 3 - 1 : 0;
-    const int wt_ar = (w >> 2) + wt_dr, wt_ac = (w & 3) + wt_dc;                       // -1 .. 4
-    const int wt_wave = ((wt_ar & 3) << 2) | (wt_ac & 3), wt_di = (wt_ar >> 2) * RPW + (wt_ac >> 2);
+    const RegionWakeTarget wt = region_wake_target(w, lane);         // a patch's 3 x 3 neighbours: per-lane constants
     const float sx = J.rb.sb.sx, sy = J.rb.sb.sy;
     const int rx0 = J.tx0 * T, ry0 = J.ty0 * T;
     int budget = J.max_sweeps;               // (per wave and phase)
@@ -180,7 +163,7 @@ __device__ void region_phase(const DevParams &P, const RegionJob &J, float *Gs, 
     const float Bphase = (MODE == MODE_LOWER) ? S.Bgate : INFINITY;
     const float rb_phase = S.rbound + J.slack;
     // words of this wave that can hold a bit at all (a block smaller than RTMAX x RTMAX leaves the upper ones empty)
-    const int nwords = min(RWW, (((nprow + 3) / 4 - 1) * RPW + (npcol + 3) / 4 + 31) / 32);
+    const int nwords = region_nwords(nprow, npcol);
     UFM_REGION_SETPRIO(UFM_REGION_PRIO);
     for (;;) {
         bool took = false;
@@ -214,7 +197,7 @@ __device__ void region_phase(const DevParams &P, const RegionJob &J, float *Gs, 
                 bits &= bits - 1;
                 took = true;
                 const int idx = wd * 32 + j;
-                const int pr = (idx / RPW) * 4 + (w >> 2), pc = (idx % RPW) * 4 + (w & 3);
+                const int pr = region_bit_row(w, idx), pc = region_bit_col(w, idx);
                 if (pr >= nprow || pc >= npcol) continue;                    // (never woken; a block smaller than RTMAX)
                 const int lx = pr * 4 + (nd >> 2), ly = pc * 4 + (nd & 3);
                 const bool arith = BPRAISE && ((seedbits >> j) & 1);            // (wave-uniform)
@@ -232,10 +215,10 @@ __device__ void region_phase(const DevParams &P, const RegionJob &J, float *Gs, 
                 const bool bnone = is_dfm<ALGO> && bpb == BP_NONE;
                 const bool goal = (lx == goal_lx) & (ly == goal_ly);
                 // wake targets: lane 0..8 = the 3x3 patches around this one (lane 4: itself).  Which wave a neighbouring patch belongs to and how far its
-                // bit lies from this patch's own do not depend on the patch (wt_*, above the loop): per burst only the position and the range test are left
-                const int npr = pr + wt_dr, npc = pc + wt_dc, ni = idx + wt_di;
-                const bool wt_ok = wt_lane & ((unsigned)npr < (unsigned)nprow) & ((unsigned)npc < (unsigned)npcol);
-                const int nwave = wt_wave, nword = wt_ok ? (ni >> 5) : -1, nbit = 1 << (ni & 31);
+                // bit lies from this patch's own do not depend on the patch (wt, above the loop): per burst only the position and the range test are left
+                const int ni = idx + wt.di;
+                const bool wt_ok = region_wake_target_ok(wt, pr, pc, nprow, npcol);
+                const int nwave = wt.wave, nword = wt_ok ? (ni >> 5) : -1, nbit = 1 << (ni & 31);
                 // admissible part of the key that does not depend on the value: hm * dist(start, patch)
                 float hd = 0.0f;
                 if (HEUR && hm != 0.0f) {
@@ -367,151 +350,55 @@ __device__ void region_phase(const DevParams &P, const RegionJob &J, float *Gs, 
     __syncthreads();
 }
 
-template <int ALGOF, int FORM>   // (the operator id, with ALGO_FOLLOW_INFO, and the form: region_phase)
-__global__ __launch_bounds__(NTHR) void k_replan_region(DevParams P, RegionJobs JS, DevCounters *host, unsigned int *flag) {
-    constexpr int ALGO = algo_of(ALGOF);
-    constexpr bool HEUR = (FORM & RF_HEUR) != 0, DBG = (FORM & RF_DEBUG) != 0;
-    __shared__ float Gs[(RN + 2) * RP];
-    __shared__ uint8_t Cb[(RN + 1) * RCP];
-    __shared__ __attribute__((aligned(16))) uint8_t Bb[RN * RBP];
-    __shared__ RegionShared S;
-    __shared__ int s_last;
-#ifdef UFM_REGION_NG0
-    constexpr int NG0 = UFM_REGION_NG0;              // (test builds: a small copy, so that the path of the tiles beyond it runs)
-#else
-    constexpr int NG0 = (46 * 1024) / (TT * 4);      // tiles of the write-back's LDS copy of what HBM holds: what the CU's 160 KB leave (46 KB; a 6 x 6 block needs 36)
-#endif
-    __shared__ float G0c[NG0 * TT];
-    __shared__ int s_wbl[RTMAX * RTMAX];  // write-back: the tiles that have something to write
-    __shared__ int s_nwb;
-    __shared__ uint8_t s_pmask[4096];     // change mask of a patch that comes with the job (<= 64 x 64 cells)
-    __shared__ int s_simd[16];               // diagnostics: the SIMD each wave runs on
-    __shared__ unsigned long long s_tb[8];   // diagnostics: the prologue's timeline
-    constexpr bool CELLS = is_dfm<ALGO>;
+// ---- the stages of k_replan_region that are functions, in the order the kernel runs them: applying the job's patches (0b), seeding the wake words,
+// re-opening held-back work between the phases, the hand-over to the queues, the end check (4), the publication (5).  What they share -- the block in
+// LDS and its wave-uniform geometry -- is one struct, built once at the top of the kernel; a stage takes from it what it reads.
+// The other stages -- staging the block (0a), beginning the step (0c), the decisions between the rounds (2), the write-back (3) with its two
+// lists of tiles, the hand-over of the touched tiles, the back-pointer tail (6), and the time stamps of the prologue -- are still the kernel's own text under their
+// "----" comments: as functions of this form each of them moved the registers of the kernel (SGPR spills, scratch) or made an instantiation longer,
+// and this kernel is held to the resource usage it had (profiles/region_stages_refactor.txt has the figures per stage).
+struct RegionBlock {
+    float *Gs; uint8_t *Cb, *Bb; RegionShared *S;       // the block's field (+ frame), cost bytes, back-pointer codes; the phases' shared state
+    uint8_t *pmask;                                     // a held patch's change mask
+    unsigned long long *tb; int *simd; int debug;       // diagnostics (the full form's alone): the prologue's timeline, the waves' SIMDs, RegionJob::debug
+    int m, gt0, ntl, rx0, ry0, rnx, rny;                // the job's map and its first tile, tiles of the block, its origin and extent in elements
+};
+// (the kernel's own stamps are its STAMP macro: the same statement)
+template <bool DBG>
+__device__ __forceinline__ void region_stamp(const RegionBlock &B, int k) { if (DBG && threadIdx.x == 0 && (B.debug & 2)) B.tb[k] = wall_clock64(); }
+// work that was held back is opened again: its patches are woken, the list of them cleared, the tiles' deferred priorities reset (q: 0 lowering, 1
+// invalidation; EVER: with them everything the invalidation swept -- it is re-lowered)
+template <bool EVER>
+__device__ __forceinline__ void region_reopen(RegionShared &S, int q) {
+    const int tid = threadIdx.x;
+    for (int i = tid; i < 16 * RWW; i += NTHR) {
+        if (EVER) { (&S.wake[0][0])[i] |= (&S.ever[0][0])[i] | (&S.defer[q][0][0])[i]; (&S.ever[0][0])[i] = 0; (&S.defer[q][0][0])[i] = 0; }
+        else { (&S.wake[0][0])[i] |= (&S.defer[q][0][0])[i]; (&S.defer[q][0][0])[i] = 0; }
+    }
+    for (int i = tid; i < RTMAX * RTMAX; i += NTHR) S.dprio[q][i] = INFBITS;
+}
+
+// ---- 0b. Graph::update (Graph.cpp:36-51) + the seeding of update() for the patches that come with the job -- what k_patch_small does for a
+// patch applied at the call.  Every rectangle lies inside the block (place_job), so the old bytes are in Cb: compare there, write the changed
+// ones to the raster, to the cost windows and to Cb; the change mask stays in LDS.  In the order the patches were handed over (they may overlap).
+template <bool CELLS, bool DBG>
+__device__ __forceinline__ void region_apply_patches(const DevParams &P, const RegionJob &J, const RegionBlock &B, int r_first, bool one_fused, const int (&pb0)[4]) {
     constexpr int COFF = CELLS ? 0 : 1;
     const int tid = threadIdx.x;
-    const RegionJob &J = JS.j[blockIdx.x];
-    const int m = J.map, gt0 = m * P.NTm;                     // the job's map and its first tile
-    const int ntl = J.ntx * J.nty;
-    // tile index of the block -> its row: tl / nty as a multiplication (exact for tl < 256, nty <= 8): the staging and write-back loops divided once per
-    // iteration and thread, ~25 instructions each
-    const int nty_magic = (65536 + J.nty - 1) / J.nty;
-    const int rx0 = J.tx0 * T, ry0 = J.ty0 * T, rnx = J.ntx * T, rny = J.nty * T;
-
-    const int debug = DBG ? J.debug : 0;                      // (the diagnostics, their time stamps included, are the full form's alone)
-    const unsigned long long t_begin = DBG ? wall_clock64() : 0ull;
-#define STAMP(k) do { if (DBG && tid == 0 && (debug & 2)) s_tb[k] = wall_clock64(); } while (0)
-    STAMP(0);
-    if (DBG && (tid & 63) == 0 && (debug & 2)) s_simd[tid >> 6] = (int)__builtin_amdgcn_s_getreg((1 << 11) | (4 << 6) | 4);   // HW_ID.SIMD_ID
-    const float hm = HEUR ? J.dyn.hm : 0.0f;                  // (the host takes a form without the term when it is 0)
-    const int thr = J.dyn.thr, focused = J.dyn.focused;
-    // ---- 0. Everything the kernel needs from memory is asked for FIRST, before anything is waited for (round 4: as five dependent steps --
-    // cost bytes, patch bytes from host memory, the seeding's returning atomics, the start elements' values behind the step bookkeeping's
-    // stores, the tiles -- the prologue took 14 us; `tools/replan_timeline.py`): the bytes of the first patch that comes with the job (host
-    // memory: the longest trip), the start elements' values (for the start's key before the patch), the count of pending seeds.
-    int r_first = -1;                                       // the first rectangle whose patch this kernel applies
-    for (int r = J.rb.nrect - 1; r >= 0; --r) if (J.psrc[r]) r_first = r;
-    // (one patch, applied here, nothing else pending: the common replan.  Its seeding needs no marks and no seed list -- see 0b)
-    const bool one_fused = J.rb.nrect == 1 && r_first == 0 && !J.batch;
-    int pb0[4] = {0, 0, 0, 0};
-    if (r_first >= 0) {
-        const int n0 = J.rb.rect[r_first][3] * J.rb.rect[r_first][4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) { const int e = tid + c * NTHR; if (e < n0) pb0[c] = J.psrc[r_first][e]; }
-    }
-    float sg = INFINITY;
-    int se_x = -1, se_y = -1;             // threads 0..3: this thread's start element (-1: none)
-    {   // (not J.rb.sb.start[tid]: indexing the kernel's arguments by thread is a memory load, waited for with the host's bytes in front of it)
-        const int e = tid == 0 ? J.rb.sb.start[0] : (tid == 1 ? J.rb.sb.start[1] : (tid == 2 ? J.rb.sb.start[2] : (tid == 3 ? J.rb.sb.start[3] : -1)));
-        if (e >= 0) { se_x = e / P.EY; se_y = e - se_x * P.EY; sg = P.G[gaddr(P, m, se_x, se_y)]; }
-    }
-    const int n_pending = P.ctr->scount;
-    const int goal_x = P.goal[2 * m], goal_y = P.goal[2 * m + 1];      // (asked for here: read where it is used, in front of the phases, it was a memory round trip of its own)
-    // ---- 0a. stage the block: the cost bytes (a patch that comes with the job is applied on top of them), the tiles (contiguous 1 KB each)
-    // with their back-pointer bytes, the 1-element frame around the block ----
-    // (Work is dealt out by wave -- a row piece of 64 cost bytes, a quarter KB of a tile -- so that which row / which tile is the wave's scalar
-    //  arithmetic, and every load of a thread is asked for before the first one is waited for: dealt out element by element, a division and
-    //  a memory round trip per element and thread, this staging took 12 us of the kernel's 160.)
-    STAMP(1);
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), ln = tid & 63;
-    {
-        const int crow = rnx + COFF, ccol = rny + COFF;
-        constexpr int KP = (RN + 64) / 64, KR = (RN + 16) / 16;          // 64-byte pieces of a row (3), rows per wave (9)
-        const uint8_t *cbase = P.cost + (size_t)m * P.cstride;
-        uint8_t cv[KP * KR];
-#pragma unroll
-        for (int j = 0; j < KP; ++j) {
-            const int c = j * 64 + ln, cy = ry0 + c - COFF;
-            const bool cok = c < ccol && cy >= 0 && cy < P.W;
-#pragma unroll
-            for (int k = 0; k < KR; ++k) {
-                const int r = wv + 16 * k, cx = rx0 + r - COFF;
-                cv[j * KR + k] = 255;
-                if (j * 64 < ccol && r < crow && cx >= 0 && cx < P.L && cok) cv[j * KR + k] = cbase[(size_t)cx * P.W + cy];
-            }
-        }
-        constexpr int CPT = TT / 256, KT = RTMAX * RTMAX * CPT / 16;                 // CPT: 64-lane float4 pieces per tile
-        float4 gv[KT];
-        unsigned int bv[KT];
-#pragma unroll
-        for (int k = 0; k < KT; ++k) {
-            const int pc = wv + 16 * k, tl = pc / CPT;
-            if (tl >= ntl) continue;
-            const int ti = (tl * nty_magic) >> 16, tj = tl - ti * J.nty, v = (pc - tl * CPT) * 64 + ln;
-            const size_t gt = (size_t)(gt0 + (J.tx0 + ti) * P.TY + J.ty0 + tj);
-            gv[k] = reinterpret_cast<const float4 *>(P.G + gt * TT)[v];
-            bv[k] = reinterpret_cast<const unsigned int *>(P.bp + gt * TT)[v];
-        }
-        // the frame (at most 4 * RN + 4 elements: one per thread)
-        static_assert(4 * RN + 4 <= NTHR, "one frame element per thread");
-        float fv = INFINITY;
-        int fo = -1;
-        if (tid < 2 * (rny + 2) + 2 * rnx) {
-            int hx, hy;
-            if (tid < rny + 2) { hx = -1; hy = tid - 1; }
-            else if (tid < 2 * (rny + 2)) { hx = rnx; hy = tid - (rny + 2) - 1; }
-            else if (tid < 2 * (rny + 2) + rnx) { hx = tid - 2 * (rny + 2); hy = -1; }
-            else { hx = tid - 2 * (rny + 2) - rnx; hy = rny; }
-            const int x = rx0 + hx, y = ry0 + hy;
-            fo = (hx + 1) * RP + hy + 1;
-            if (x >= 0 && y >= 0 && x < P.TX * T && y < P.TY * T) fv = P.G[gaddr(P, m, x, y)];
-        }
-        STAMP(7);
-#pragma unroll
-        for (int j = 0; j < KP; ++j) {
-            const int c = j * 64 + ln;
-#pragma unroll
-            for (int k = 0; k < KR; ++k) {
-                const int r = wv + 16 * k;
-                if (j * 64 < ccol && r < crow && c < ccol) Cb[r * RCP + c] = cv[j * KR + k];
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < KT; ++k) {
-            const int pc = wv + 16 * k, tl = pc / CPT;
-            if (tl >= ntl) continue;
-            const int ti = (tl * nty_magic) >> 16, tj = tl - ti * J.nty, e = ((pc - tl * CPT) * 64 + ln) * 4;
-            float *g = &Gs[(ti * T + e / T + 1) * RP + tj * T + e % T + 1];
-            g[0] = gv[k].x; g[1] = gv[k].y; g[2] = gv[k].z; g[3] = gv[k].w;
-            *reinterpret_cast<unsigned int *>(&Bb[(ti * T + e / T) * RBP + tj * T + e % T]) = bv[k];
-        }
-        if (fo >= 0) Gs[fo] = fv;
-    }
-    // ---- 0b. Graph::update (Graph.cpp:36-51) + the seeding of update() for the patches that come with the job -- what k_patch_small does for a
-    // patch applied at the call.  Every rectangle lies inside the block (place_job), so the old bytes are in Cb: compare there, write the changed
-    // ones to the raster, to the cost windows and to Cb; the change mask stays in LDS.  In the order the patches were handed over (they may overlap).
+    uint8_t *Cb = B.Cb, *s_pmask = B.pmask;
+    const int m = B.m, rx0 = B.rx0, ry0 = B.ry0;
     for (int r = 0; r < J.rb.nrect; ++r) {
         if (!J.psrc[r]) continue;
         const int *qr = J.rb.rect[r];                       // {map, x, y, w, h}
         const int px = qr[1], py = qr[2], pw = qr[3], ph = qr[4];
-        const unsigned pw_magic = ((1u << 20) + (unsigned)pw - 1u) / (unsigned)pw;      // (patches are at most 64 x 64 cells: host side)
+        const unsigned pw_magic = region_dense_magic(pw);      // (a patch that comes with the job is at most REGION_HELD_EDGE cells wide and high)
         __syncthreads();                                    // Cb staged / the previous rectangle's seeds read
-        STAMP(2);
+        region_stamp<DBG>(B, 2);
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             const int e = tid + c * NTHR;
             if (e >= pw * ph) continue;
-            const int i = (int)(((unsigned)e * pw_magic) >> 20), j = e - i * pw;      // (e / pw: exact for e < 4400, pw <= 65)
+            const int i = region_dense_row(e, pw_magic), j = e - i * pw;
             uint8_t *cb = &Cb[(px + i - rx0 + COFF) * RCP + (py + j - ry0 + COFF)];
             const uint8_t nv = (r == r_first) ? (uint8_t)pb0[c] : J.psrc[r][e];
             const uint8_t ch = *cb != nv;
@@ -519,17 +406,17 @@ __global__ __launch_bounds__(NTHR) void k_replan_region(DevParams P, RegionJobs 
             if (ch) { *cb = nv; P.cost[(size_t)m * P.cstride + (size_t)(px + i) * P.W + (py + j)] = nv; cost_window_store(P, m, px + i, py + j, nv); }
         }
         __syncthreads();
-        STAMP(3);
+        region_stamp<DBG>(B, 3);
         const int ne = CELLS ? pw * ph : (pw + 1) * (ph + 1);
         if (one_fused) {
             // num_nodes_updated (FD impl:138, DFM impl:109): the elements a changed cell touches.  One patch, nothing else pending: no element can
             // have been counted already (the marks, which are for that, are all clear between steps and stay clear), and every seeded tile lies
             // inside the block (no seed list).  Counted per wave, one atomic each.
             const int ew = CELLS ? pw : pw + 1;
-            const unsigned ew_magic = ((1u << 20) + (unsigned)ew - 1u) / (unsigned)ew;
+            const unsigned ew_magic = region_dense_magic(ew);
             int cnt = 0;
             for (int e = tid; e < ne; e += NTHR) {
-                const int i = (int)(((unsigned)e * ew_magic) >> 20), j = e - i * ew;
+                const int i = region_dense_row(e, ew_magic), j = e - i * ew;
                 bool ch;
                 if (!CELLS) ch = (i > 0 && j > 0 && s_pmask[(i - 1) * pw + j - 1]) || (i > 0 && j < pw && s_pmask[(i - 1) * pw + j]) ||
                                  (i < ph && j > 0 && s_pmask[i * pw + j - 1]) || (i < ph && j < pw && s_pmask[i * pw + j]);
@@ -543,256 +430,38 @@ __global__ __launch_bounds__(NTHR) void k_replan_region(DevParams P, RegionJobs 
         }
     }
     if (J.rb.nrect && J.psrc[J.rb.nrect - 1]) __syncthreads();      // (the seeds' list entries and counts are read below)
-    STAMP(4);
-    // ---- 0c. what k_replan_begin does: step bookkeeping, mark reset, the seeds, the invalidation bound ----
-    if (tid == 0 && !J.batch) *P.dyn = J.dyn;      // (a batch: the host has put them in place before the launch -- other workgroups read them too)
-    if (!J.batch) step_begin(P, J.rb.sb);
-    if (!one_fused)
-        for (int r = 0; r < J.rb.nrect; ++r) {
-            const int *qr = J.rb.rect[r];
-            for (int e = tid; e < (qr[3] + 1) * (qr[4] + 1); e += NTHR) clear_mark(P, qr[0], qr[1], qr[2], qr[3], qr[4], e);
-        }
-    for (int i = tid; i < (int)(sizeof(RegionShared) / sizeof(int)); i += NTHR) reinterpret_cast<int *>(&S)[i] = 0;
-    __syncthreads();
-    STAMP(5);
-    for (int i = tid; i < 2 * RTMAX * RTMAX; i += NTHR) (&S.dprio[0][0])[i] = INFBITS;
-    for (int i = tid; i < RFRAME; i += NTHR) { S.actL[i] = INFBITS; S.actR[i] = INFBITS; }
-    for (int i = tid; i < 16 * RWW * 32; i += NTHR) (&S.pkey[0][0])[i] = INFBITS;
-    if (tid == 0) { S.rmin = INFBITS; S.m_r = INFBITS; }
-    {   // pending seeds of this map (all consumed): tiles inside the block are handled here, any other goes to the queue
-        // (n_pending was read before the patches of this job were seeded: the general seeding above appends to the list)
-        const int n = one_fused ? n_pending : P.ctr->scount;
-        for (int i = tid; i < n; i += NTHR) {
-            const int gt = P.slist[i];
-            if (gt / P.NTm != m) continue;
-            const int tx = (gt - gt0) / P.TY, ty = (gt - gt0) - tx * P.TY;
-            P.sflag[gt] = 0;
-            if (tx < J.tx0 || tx >= J.tx0 + J.ntx || ty < J.ty0 || ty >= J.ty0 + J.nty) activate(P, Q_RAISE, J.rb.k_raise, gt, 0);
-        }
-        __syncthreads();
-        STAMP(6);
-        if (tid == 0 && !J.batch) { P.ctr->scount = 0; P.ctr->done = 0; }   // (a batch: the last workgroup, when everybody has read the list)
-        if (tid < 64) {
-            // the start's key before the patch (start_bound(), from the values asked for at the top): one start element per lane 0..3 (one thread
-            // after the other -- four divisions, four hypotf -- this was a microsecond in front of the phases), the largest key by two shuffles
-            float key = 0.0f, dist = 0.0f;
-            int off = -1;
-            if (se_x >= 0) {
-                if (HEUR) dist = hm * hypotf(J.rb.sb.sx - (float)se_x, J.rb.sb.sy - (float)se_y);
-                if (sg < INFINITY) key = sg + dist;
-                if (se_x >= rx0 && se_x < rx0 + rnx && se_y >= ry0 && se_y < ry0 + rny) off = (se_x - rx0 + 1) * RP + (se_y - ry0 + 1);
-            }
-            if (tid < 4) { S.soff[tid] = off; S.sdist[tid] = dist; }
-            const bool in = __builtin_amdgcn_ballot_w64(off >= 0) != 0ull;
-            float b0 = fmaxf(key, __shfl_xor(key, 1));
-            b0 = fmaxf(b0, __shfl_xor(b0, 2));
-            if (tid == 0) {
-                b0 = b0 > 0.0f ? b0 : INFINITY;
-                S.B0 = b0;
-                S.rbound = focused ? b0 + J.rb.band : INFINITY;
-                S.any_start_in = in ? 1 : 0;
-            }
-        }
-    }
-
-    if (DBG && tid == 0) { S.tstamp[0] = t_begin; S.tstamp[1] = wall_clock64(); S.tstamp[2] = S.tstamp[1]; }
-    // the seeds: every patch that holds an element of a consumed rectangle (a superset of the changed cells' elements;
-    // a sweep that finds nothing to do costs a fraction of a microsecond)
-    __syncthreads();
+}
+// the seeds: every patch that holds an element of a consumed rectangle (a superset of the changed cells' elements;
+// a sweep that finds nothing to do costs a fraction of a microsecond)
+template <bool CELLS>
+__device__ __forceinline__ void region_seed_wake(const RegionJob &J, const RegionBlock &B) {
+    const int tid = threadIdx.x;
+    float *Gs = B.Gs;
+    RegionShared &S = *B.S;
+    const int rx0 = B.rx0, ry0 = B.ry0, rnx = B.rnx, rny = B.rny;
     for (int r = 0; r < J.rb.nrect; ++r) {
         const int *qr = J.rb.rect[r];                       // {map, x, y, w, h}: cells x..x+h-1, y..y+w-1
-        const int ex0 = qr[1] - rx0, ex1 = qr[1] + qr[4] - (CELLS ? 1 : 0) - rx0, ey0 = qr[2] - ry0, ey1 = qr[2] + qr[3] - (CELLS ? 1 : 0) - ry0;
-        const int p0 = max(ex0, 0) / 4, p1 = min(ex1, rnx - 1) / 4, c0 = max(ey0, 0) / 4, c1 = min(ey1, rny - 1) / 4;
+        const RegionPatchRange sr = region_seed_range(qr, CELLS, rx0, ry0, rnx, rny);
+        const int p0 = sr.p0, p1 = sr.p1, c0 = sr.c0, c1 = sr.c1;
         const int np = (p1 - p0 + 1) * (c1 - c0 + 1);
         for (int i = tid; i < np; i += NTHR) {
             const int pr = p0 + i / (c1 - c0 + 1), pc = c0 + i % (c1 - c0 + 1);
-            const int ni = (pr >> 2) * RPW + (pc >> 2);
-            atomicOr(&S.wake[((pr & 3) << 2) | (pc & 3)][ni >> 5], 1 << (ni & 31));
-            atomicOr(&S.seed[((pr & 3) << 2) | (pc & 3)][ni >> 5], 1 << (ni & 31));
+            const RegionWakeBit wb = region_wake_bit(pr, pc);
+            atomicOr(&S.wake[wb.wave][wb.word], wb.bit);
+            atomicOr(&S.seed[wb.wave][wb.word], wb.bit);
             S.traised[(pr / TP) * J.nty + pc / TP] = 1;      // a seeded tile is invalidated without a bound (the launch chain queues seeds with priority 0)
         }
     }
     if (tid < 4) S.swas[tid] = (S.soff[tid] >= 0 && Gs[S.soff[tid]] < INFINITY) ? 1 : 0;
-    __syncthreads();
-    const int goal_lx = goal_x - rx0, goal_ly = goal_y - ry0;
-
-    // ---- 2. invalidate, lower; again while an invalidation that was held back lies below the start's new key ----
-    for (int round = 0;; ++round) {
-        for (;;) {
-            region_phase<ALGOF, MODE_RAISE, FORM>(P, J, Gs, Cb, Bb, S, thr, hm, focused, goal_lx, goal_ly);
-            // a tile that lost a value after some of its patches had been held back: those patches again
-            const int again_t = __syncthreads_or(tid < ntl && S.traised[tid] && S.dprio[1][tid] != INFBITS) && !S.giveup;
-            __syncthreads();
-            if (!again_t) break;
-            for (int i = tid; i < 16 * RWW; i += NTHR) { (&S.wake[0][0])[i] |= (&S.defer[1][0][0])[i]; (&S.defer[1][0][0])[i] = 0; }
-            for (int i = tid; i < RTMAX * RTMAX; i += NTHR) S.dprio[1][i] = INFBITS;
-            __syncthreads();
-        }
-        if (DBG && tid == 0 && round == 0) S.tstamp[3] = wall_clock64();
-        // everything the invalidation swept is re-lowered (plus, in later rounds, what lowering had to hold back)
-        for (int i = tid; i < 16 * RWW; i += NTHR) {
-            (&S.wake[0][0])[i] |= (&S.ever[0][0])[i] | (&S.defer[0][0][0])[i];
-            (&S.ever[0][0])[i] = 0; (&S.defer[0][0][0])[i] = 0;
-        }
-        for (int i = tid; i < RTMAX * RTMAX; i += NTHR) S.dprio[0][i] = INFBITS;
-        if (tid == 0) {
-            S.dkey = INFBITS;
-            S.Bsub = focused ? region_lower_bound(Gs, S) : INFINITY;
-            // the first band: everything below the smallest value that was taken away, plus one band width (a step without
-            // invalidations is not ordered: its few lowered values sit around the patch)
-            S.theta = (round == 0) ? ((S.rmin != INFBITS) ? __int_as_float(S.rmin) + J.delta : INFINITY) : S.theta;
-            S.Bgate = fminf(S.Bsub + J.slack, S.theta);
-        }
-        __syncthreads();
-        for (int sub = 0;; ++sub) {
-            region_phase<ALGO, MODE_LOWER, FORM>(P, J, Gs, Cb, Bb, S, thr, hm, focused, goal_lx, goal_ly);
-            // the smallest key the sub-round leaves held back: over the patches' last bursts (S.pkey)
-            for (int i = tid; i < 16 * RWW * 32; i += NTHR) { const int k = (&S.pkey[0][0])[i]; if (k != INFBITS) atomicMin(&S.dkey, k); }
-            __syncthreads();
-            // the start's key may have risen while results were being held back against an earlier value of it
-            if (tid == 0) {
-                const float B = focused ? region_lower_bound(Gs, S) : INFINITY;
-                const int m = S.dkey;
-                bool again = !S.giveup && m != INFBITS && (__int_as_float(m) < B || B == INFINITY);
-                if (again && sub >= 4096) { again = false; S.giveup = 1; }   // (never seen; what is dirty goes to the queues)
-                S.again = again ? 1 : 0;
-                S.Bsub = B;
-                if (again) S.theta = fmaxf(S.theta, __int_as_float(m)) + J.delta;    // the next band starts where work is waiting
-                S.Bgate = fminf(S.Bsub + J.slack, S.theta);
-            }
-            __syncthreads();
-            const int again_l = S.again;
-            __syncthreads();                    // (thread 0 overwrites the word below: everyone has read it first)
-            if (!again_l) break;
-            if (DBG && tid == 0) ++S.dbg[2];
-            for (int i = tid; i < 16 * RWW; i += NTHR) { (&S.wake[0][0])[i] |= (&S.defer[0][0][0])[i]; (&S.defer[0][0][0])[i] = 0; }
-            for (int i = tid; i < RTMAX * RTMAX; i += NTHR) S.dprio[0][i] = INFBITS;
-            if (tid == 0) S.dkey = INFBITS;
-            __syncthreads();
-        }
-        if (tid < ntl && S.dprio[1][tid] != INFBITS) atomicMin(&S.m_r, S.dprio[1][tid]);     // (S.m_r: INFBITS here, reset below)
-        __syncthreads();
-        if (tid == 0) {
-            const float B = focused ? region_lower_bound(Gs, S) : INFINITY;
-            const int m = S.m_r;
-            S.m_r = INFBITS;
-            bool again = !S.giveup && focused && m != INFBITS && __int_as_float(m) < B + J.slack;   // lowering reaches the key plus one move
-            if (again && round >= 14) { again = false; S.giveup = 1; }
-            if (again) S.rbound = fmaxf(B, S.rbound) + J.rb.band;
-            S.again = again ? 1 : 0;
-        }
-        __syncthreads();
-        const int again_r = S.again;
-        __syncthreads();
-        if (!again_r) break;
-        if (DBG && tid == 0) ++S.dbg[3];
-        for (int i = tid; i < 16 * RWW; i += NTHR) { (&S.wake[0][0])[i] |= (&S.defer[1][0][0])[i]; (&S.defer[1][0][0])[i] = 0; }
-        for (int i = tid; i < RTMAX * RTMAX; i += NTHR) S.dprio[1][i] = INFBITS;
-        __syncthreads();
-    }
-
-    if (DBG && tid == 0) S.tstamp[4] = wall_clock64();
-    // ---- 3. write back: changed values, the rings of the neighbours they border, what the frame has to hear ----
-    // frame tile index of the tile at block coordinates (ti, tj), ti in -1..ntx, tj in -1..nty (one of them outside)
-    auto frame_index = [&](int ti, int tj) {
-        if (ti < 0) return tj + 1;                                   // top row: 0 .. nty+1
-        if (ti >= J.ntx) return (J.nty + 2) + tj + 1;                // bottom row
-        if (tj < 0) return 2 * (J.nty + 2) + ti;                     // left column
-        return 2 * (J.nty + 2) + J.ntx + ti;                         // right column
-    };
-    static_assert(NTHR == 1024 && TT % 64 == 0 && RBP % 4 == 0, "the block kernel deals its staging and write-back out by wave");
-    // (Round 4: this used to be two loops of 16 iterations per thread over ALL tiles of the largest block, unrolled so that the values HBM holds could wait in
-    //  registers between them -- 12 000 instructions of which a replan executes a sixth, fetched cold at every launch.  Now: the tiles that have something to
-    //  write are listed, what HBM holds of them goes straight into LDS (no register held, every load in flight at once), and one loop walks the list.)
-    constexpr int UPT = TT / 64;                                        // units (64 consecutive elements = one wave) per tile
-    const int wvw = __builtin_amdgcn_readfirstlane(tid >> 6), lnw = tid & 63;
-    if (tid < 64) {
-        const bool has = tid < ntl && S.tflag[tid];      // (the tiles that only hold renewed back-pointers: the tail's list, behind the flag)
-        const unsigned long long hm_ = __builtin_amdgcn_ballot_w64(has);
-        if (has) s_wbl[__popcll(hm_ & ((1ull << tid) - 1ull))] = tid;
-        if (tid == 0) s_nwb = __popcll(hm_);
-    }
-    __syncthreads();
-    const int nunits = s_nwb * UPT;
-    auto unit_tile = [&](int u, int &k, int &part, int &tl, int &ti, int &tj) {      // (all wave-uniform)
-        k = u / UPT; part = u - k * UPT; tl = __builtin_amdgcn_readfirstlane(s_wbl[k]);
-        ti = (tl * nty_magic) >> 16; tj = tl - ti * J.nty;
-    };
-    {
-        typedef __attribute__((address_space(3))) void *lds_ptr;
-        typedef const __attribute__((address_space(1))) void *glb_ptr;
-#pragma unroll 1
-        for (int u = wvw; u < nunits; u += 16) {
-            int k, part, tl, ti, tj;
-            unit_tile(u, k, part, tl, ti, tj);
-            if (k >= NG0) continue;
-            const size_t gt = (size_t)(gt0 + (J.tx0 + ti) * P.TY + J.ty0 + tj);
-            __builtin_amdgcn_global_load_lds((glb_ptr)(P.G + gt * TT + part * 64 + lnw), (lds_ptr)(G0c + k * TT + part * 64), 4, 0, 0);
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __syncthreads();
-    int n_exp = 0;
-#pragma unroll 1
-    for (int u = wvw; u < nunits; u += 16) {
-        int k, part, tl, ti, tj;
-        unit_tile(u, k, part, tl, ti, tj);
-        const int e = part * 64 + lnw;
-        const int tx = J.tx0 + ti, ty = J.ty0 + tj, gt = gt0 + tx * P.TY + ty;
-        const int io_r = e / T, io_c = e % T;
-        float gl0;
-        if (k < NG0) gl0 = G0c[k * TT + e];
-        else { gl0 = P.G[(size_t)gt * TT + e]; P.Gprev[(size_t)gt * TT + e] = gl0; }      // (more changed tiles than the LDS copy holds: their old values go to the snapshot at once)
-        const float gf = Gs[(ti * T + io_r + 1) * RP + tj * T + io_c + 1];
-        if (gf == gl0) continue;
-        ++n_exp;
-        P.G[(size_t)gt * TT + e] = gf;
-        const int er = (io_r == 0) ? -1 : ((io_r == T - 1) ? 1 : 0);
-        const int ec = (io_c == 0) ? -1 : ((io_c == T - 1) ? 1 : 0);
-        const bool rok = er && tx + er >= 0 && tx + er < P.TX, cok = ec && ty + ec >= 0 && ty + ec < P.TY;
-        if (rok) P.ring[(size_t)(gt + er * P.TY) * RING + (er < 0 ? RING_BOT : RING_TOP) + io_c] = gf;
-        if (cok) P.ring[(size_t)(gt + ec) * RING + (ec < 0 ? RING_RIGHT : RING_LEFT) + io_r] = gf;
-        if (rok && cok) P.ring[(size_t)(gt + er * P.TY + ec) * RING + RING_CORNER + (er < 0 ? 2 : 0) + (ec < 0 ? 1 : 0)] = gf;
-        // neighbours outside the block: lowered value -> lowering queue, lost / raised value -> invalidation queue,
-        // each only if an element of that neighbour (the frame, as staged) can be concerned at all (causality, see k_relax)
-        const bool out_r = rok && (ti + er < 0 || ti + er >= J.ntx), out_c = cok && (tj + ec < 0 || tj + ec >= J.nty);
-        if (!(out_r || out_c)) continue;
-        const int lxr = ti * T + io_r + 1, lyc = tj * T + io_c + 1;          // position in Gs
-        const int cl = max(io_c - 1, 0) - io_c, ch = min(io_c + 1, T - 1) - io_c;   // columns / rows of the edge neighbour itself
-        const int rl = max(io_r - 1, 0) - io_r, rh = min(io_r + 1, T - 1) - io_r;
-        const float lo = fminf(gf, gl0);
-        const bool lowered = gf < gl0;
-        const int pb = __float_as_int(lowered ? gf : gl0);
-        auto concerned = [&](float a, float b, float c) {
-            if (lowered) return lo < fmaxf(fmaxf(a, b), c);                  // someone above the new value
-            const float fa = a < INFINITY ? a : -INFINITY, fb = b < INFINITY ? b : -INFINITY, fc = c < INFINITY ? c : -INFINITY;
-            return gl0 < fmaxf(fmaxf(fa, fb), fc);                          // someone (finite) above the old value may have leaned on it
-        };
-        if (out_r) {
-            const float *h = Gs + (lxr + er) * RP + lyc;
-            if (concerned(h[cl], h[0], h[ch])) atomicMin(lowered ? &S.actL[frame_index(ti + er, tj)] : &S.actR[frame_index(ti + er, tj)], pb);
-        }
-        if (out_c) {
-            const float *h = Gs + lxr * RP + lyc + ec;
-            if (concerned(h[rl * RP], h[0], h[rh * RP])) atomicMin(lowered ? &S.actL[frame_index(ti, tj + ec)] : &S.actR[frame_index(ti, tj + ec)], pb);
-        }
-        if (rok && cok && (out_r || out_c)) {                               // the diagonal neighbour
-            const int di = ti + er, dj = tj + ec;
-            if (di < 0 || di >= J.ntx || dj < 0 || dj >= J.nty) {
-                const float hv = Gs[(lxr + er) * RP + lyc + ec];
-                if (concerned(hv, hv, hv)) atomicMin(lowered ? &S.actL[frame_index(di, dj)] : &S.actR[frame_index(di, dj)], pb);
-            }
-        }
-    }
-    if (n_exp) atomicAdd(&S.expanded, n_exp);
-    __syncthreads();
-    // frame tiles -> queues; held-back results -> park lists; what a budget overrun left dirty -> queues
-    for (int i = tid; i < 2 * (J.nty + 2) + 2 * J.ntx; i += NTHR) {
-        int ti, tj;
-        if (i < J.nty + 2) { ti = -1; tj = i - 1; }
-        else if (i < 2 * (J.nty + 2)) { ti = J.ntx; tj = i - (J.nty + 2) - 1; }
-        else if (i < 2 * (J.nty + 2) + J.ntx) { ti = i - 2 * (J.nty + 2); tj = -1; }
-        else { ti = i - 2 * (J.nty + 2) - J.ntx; tj = J.nty; }
+}
+// frame tiles -> queues; held-back results -> park lists; what a budget overrun left dirty -> queues
+__device__ __forceinline__ void region_hand_over(const DevParams &P, const RegionJob &J, const RegionBlock &B) {
+    const int tid = threadIdx.x;
+    RegionShared &S = *B.S;
+    const int gt0 = B.gt0, ntl = B.ntl;
+    for (int i = tid; i < region_frame_count(J.ntx, J.nty); i += NTHR) {
+        const RegionFramePos fp = region_frame_at(i, J.ntx, J.nty);
+        const int ti = fp.a, tj = fp.b;
         const int tx = J.tx0 + ti, ty = J.ty0 + tj;
         if (tx < 0 || ty < 0 || tx >= P.TX || ty >= P.TY) continue;
         const int gt = gt0 + tx * P.TY + ty;
@@ -808,20 +477,23 @@ __global__ __launch_bounds__(NTHR) void k_replan_region(DevParams P, RegionJobs 
         for (int i = tid; i < 16 * RWW * 32; i += NTHR) {
             const int w = i / (RWW * 32), r = i % (RWW * 32);
             if (!(S.wake[w][r >> 5] & (1 << (r & 31)))) continue;
-            const int pr = (r / RPW) * 4 + (w >> 2), pc = (r % RPW) * 4 + (w & 3);
+            const int pr = region_bit_row(w, r), pc = region_bit_col(w, r);
             if (pr >= J.ntx * TP || pc >= J.nty * TP) continue;
             const int gt = gt0 + (J.tx0 + pr / TP) * P.TY + J.ty0 + pc / TP;
             activate(P, Q_RAISE, J.rb.k_raise, gt, 0);      // invalidation first, then (k_touched_to_active) lowering
             activate(P, Q_LOWER, J.k_lower, gt, 0);
         }
     }
-    // (one workgroup of a batch reads what another one queued: agent scope; a single map's end check only reads what this very
-    //  workgroup wrote -- its loads are agent-scope loads from the XCD's L2, where its stores are once they have been acknowledged)
-    if (J.batch) __threadfence(); else __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __syncthreads();
-
-    if (DBG && tid == 0) S.tstamp[5] = wall_clock64();
-    // ---- 4. the device-side end condition (as k_replan_end): is anything left below the start's key? ----
+}
+// ---- 4. the device-side end condition (as k_replan_end): is anything left below the start's key?  (S.done) ----
+template <bool DBG>
+__device__ __forceinline__ void region_end_check(const DevParams &P, const RegionJob &J, const RegionBlock &X, int focused) {
+    const int tid = threadIdx.x;
+    float *Gs = X.Gs;
+    RegionShared &S = *X.S;
+    const int m = X.m, gt0 = X.gt0, ntl = X.ntl, debug = X.debug;
+    [[maybe_unused]] const unsigned long long *s_tb = X.tb;
+    [[maybe_unused]] const int *s_simd = X.simd;
     if (tid == 0) { S.m_r = INFBITS; S.m_l = INFBITS; }
     __syncthreads();
     {
@@ -913,31 +585,19 @@ __global__ __launch_bounds__(NTHR) void k_replan_region(DevParams P, RegionJobs 
         }
         __syncthreads();
     }
-    // not done: the launch chain takes over; the tiles changed here join the step's touched list with their values
-    // as of the start of the step (num_nodes_expanded is counted against that snapshot at the end of the step)
-    if (!S.done) {
-#pragma unroll 1
-        for (int u = wvw; u < nunits; u += 16) {
-            int k, part, tl, ti, tj;
-            unit_tile(u, k, part, tl, ti, tj);
-            const int e = part * 64 + lnw;
-            const int gt = gt0 + (J.tx0 + ti) * P.TY + J.ty0 + tj;
-            if (k < NG0) P.Gprev[(size_t)gt * TT + e] = G0c[k * TT + e];
-            if (e == 0) {
-                P.fresh[gt] = 0;
-                if (atomicAdd(&P.touched[gt], 1) == 0) P.tlist[atomicAdd(&P.ctr->tcount, 1)] = gt;
-            }
-        }
-    }
-    if (J.batch) __threadfence();          // (a single map: the kernel's end, or thread 0's system-scope release below, publishes)
-    __syncthreads();
-    // ---- 5. publish.  Everything the host reads (the counters) and everything it may follow up on without a kernel of this stream in between
-    // is in place; what is left -- the back-pointer bytes -- has no reader that is not ordered behind this kernel on the engine's stream:
-    // the next k_replan_region's staging, k_relax's invalidation, k_finalize_bp, k_info_stored and the check-info kernel, the delta scan, the
-    // path kernels and the hipMemsetAsync of a re-initialisation are all submitted to it, the engine has no second stream, and the calls that
-    // free or regrow device memory synchronise it first.  So the host leaves step() here and prepares the next call while the tail runs (as
-    // finalize_bp(1) behind k_replan_end's publication does for the launch chain's steps, fused_end()).  The tail writes P.bp -- and, with the
-    // diagnostics on, its time stamp -- and nothing else: not `host`, not `flag`, no field of P.ctr.
+}
+// ---- 5. publish.  Everything the host reads (the counters) and everything it may follow up on without a kernel of this stream in between
+// is in place; what is left -- the back-pointer bytes -- has no reader that is not ordered behind this kernel on the engine's stream:
+// the next k_replan_region's staging, k_relax's invalidation, k_finalize_bp, k_info_stored and the check-info kernel, the delta scan, the
+// path kernels and the hipMemsetAsync of a re-initialisation are all submitted to it, the engine has no second stream, and the calls that
+// free or regrow device memory synchronise it first.  So the host leaves step() here and prepares the next call while the tail runs (as
+// finalize_bp(1) behind k_replan_end's publication does for the launch chain's steps, fused_end()).  The tail writes P.bp -- and, with the
+// diagnostics on, its time stamp -- and nothing else: not `host`, not `flag`, no field of P.ctr.
+template <bool DBG>
+__device__ __forceinline__ void region_publish(const DevParams &P, const RegionJob &J, const RegionBlock &B, DevCounters *host, unsigned int *flag, int &s_last) {
+    const int tid = threadIdx.x;
+    const RegionShared &S = *B.S;
+    const int debug = B.debug;
     if (J.batch) {             // the last workgroup to get here publishes for all of them; the others go on to their tails
         if (tid == 0) s_last = (atomicAdd(&P.ctr->fin_blocks, 1) == (int)gridDim.x - 1);
         __syncthreads();
@@ -965,6 +625,384 @@ __global__ __launch_bounds__(NTHR) void k_replan_region(DevParams P, RegionJobs 
             __hip_atomic_store(flag, J.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
         }
     }
+}
+
+template <int ALGOF, int FORM>   // (the operator id, with ALGO_FOLLOW_INFO, and the form: region_phase)
+__global__ __launch_bounds__(NTHR) void k_replan_region(DevParams P, RegionJobs JS, DevCounters *host, unsigned int *flag) {
+    constexpr int ALGO = algo_of(ALGOF);
+    constexpr bool HEUR = (FORM & RF_HEUR) != 0, DBG = (FORM & RF_DEBUG) != 0;
+    __shared__ float Gs[(RN + 2) * RP];
+    __shared__ uint8_t Cb[(RN + 1) * RCP];
+    __shared__ __attribute__((aligned(16))) uint8_t Bb[RN * RBP];
+    __shared__ RegionShared S;
+    __shared__ int s_last;
+#ifdef UFM_REGION_NG0
+    constexpr int NG0 = UFM_REGION_NG0;              // (test builds: a small copy, so that the path of the tiles beyond it runs)
+#else
+    constexpr int NG0 = (46 * 1024) / (TT * 4);      // tiles of the write-back's LDS copy of what HBM holds: what the CU's 160 KB leave (46 KB; a 6 x 6 block needs 36)
+#endif
+    __shared__ float G0c[NG0 * TT];
+    __shared__ int s_wbl[RTMAX * RTMAX];  // write-back: the tiles that have something to write
+    __shared__ int s_nwb;
+    __shared__ uint8_t s_pmask[REGION_HELD_EDGE * REGION_HELD_EDGE];     // change mask of a patch that comes with the job
+    static_assert(REGION_HELD_EDGE * REGION_HELD_EDGE <= 4 * NTHR, "a held patch's cells: four per thread (pb0)");
+    __shared__ int s_simd[16];               // diagnostics: the SIMD each wave runs on
+    __shared__ unsigned long long s_tb[8];   // diagnostics: the prologue's timeline
+    constexpr bool CELLS = is_dfm<ALGO>;
+    constexpr int COFF = CELLS ? 0 : 1;
+    const int tid = threadIdx.x;
+    const RegionJob &J = JS.j[blockIdx.x];
+    const int m = J.map, gt0 = m * P.NTm;                     // the job's map and its first tile
+    const int ntl = J.ntx * J.nty;
+    const int nty_magic = region_nty_magic(J.nty);            // tile index of the block -> its row (region_tile_row)
+    const int rx0 = J.tx0 * T, ry0 = J.ty0 * T, rnx = J.ntx * T, rny = J.nty * T;
+
+    const int debug = DBG ? J.debug : 0;                      // (the diagnostics, their time stamps included, are the full form's alone)
+    const unsigned long long t_begin = DBG ? wall_clock64() : 0ull;
+    const RegionBlock B{Gs, Cb, Bb, &S, s_pmask, s_tb, s_simd, debug, m, gt0, ntl, rx0, ry0, rnx, rny};
+#define STAMP(k) do { if (DBG && tid == 0 && (debug & 2)) s_tb[k] = wall_clock64(); } while (0)
+    STAMP(0);
+    if (DBG && (tid & 63) == 0 && (debug & 2)) s_simd[tid >> 6] = (int)__builtin_amdgcn_s_getreg((1 << 11) | (4 << 6) | 4);   // HW_ID.SIMD_ID
+    const float hm = HEUR ? J.dyn.hm : 0.0f;                  // (the host takes a form without the term when it is 0)
+    const int thr = J.dyn.thr, focused = J.dyn.focused;
+    // ---- 0. Everything the kernel needs from memory is asked for FIRST, before anything is waited for (round 4: as five dependent steps --
+    // cost bytes, patch bytes from host memory, the seeding's returning atomics, the start elements' values behind the step bookkeeping's
+    // stores, the tiles -- the prologue took 14 us; `tools/replan_timeline.py`): the bytes of the first patch that comes with the job (host
+    // memory: the longest trip), the start elements' values (for the start's key before the patch), the count of pending seeds.
+    int r_first = -1;                                       // the first rectangle whose patch this kernel applies
+    for (int r = J.rb.nrect - 1; r >= 0; --r) if (J.psrc[r]) r_first = r;
+    // (one patch, applied here, nothing else pending: the common replan.  Its seeding needs no marks and no seed list -- see 0b)
+    const bool one_fused = J.rb.nrect == 1 && r_first == 0 && !J.batch;
+    int pb0[4] = {0, 0, 0, 0};
+    if (r_first >= 0) {
+        const int n0 = J.rb.rect[r_first][3] * J.rb.rect[r_first][4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) { const int e = tid + c * NTHR; if (e < n0) pb0[c] = J.psrc[r_first][e]; }
+    }
+    float sg = INFINITY;
+    int se_x = -1, se_y = -1;             // threads 0..3: this thread's start element (-1: none)
+    {   // (not J.rb.sb.start[tid]: indexing the kernel's arguments by thread is a memory load, waited for with the host's bytes in front of it)
+        const int e = tid == 0 ? J.rb.sb.start[0] : (tid == 1 ? J.rb.sb.start[1] : (tid == 2 ? J.rb.sb.start[2] : (tid == 3 ? J.rb.sb.start[3] : -1)));
+        if (e >= 0) { se_x = e / P.EY; se_y = e - se_x * P.EY; sg = P.G[gaddr(P, m, se_x, se_y)]; }
+    }
+    const int n_pending = P.ctr->scount;
+    const int goal_x = P.goal[2 * m], goal_y = P.goal[2 * m + 1];      // (asked for here: read where it is used, in front of the phases, it was a memory round trip of its own)
+    STAMP(1);
+    // ---- 0a. stage the block: the cost bytes (a patch that comes with the job is applied on top of them), the tiles (contiguous 1 KB each)
+    // with their back-pointer bytes, the 1-element frame around the block ----
+    // (Work is dealt out by wave -- a row piece of 64 cost bytes, a quarter KB of a tile -- so that which row / which tile is the wave's scalar
+    //  arithmetic, and every load of a thread is asked for before the first one is waited for: dealt out element by element, a division and
+    //  a memory round trip per element and thread, this staging took 12 us of the kernel's 160.)
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), ln = tid & 63;
+    {
+        const int crow = rnx + COFF, ccol = rny + COFF;
+        constexpr int KP = (RN + 64) / 64, KR = (RN + 16) / 16;          // 64-byte pieces of a row (3), rows per wave (9)
+        const uint8_t *cbase = P.cost + (size_t)m * P.cstride;
+        uint8_t cv[KP * KR];
+#pragma unroll
+        for (int j = 0; j < KP; ++j) {
+            const int c = j * 64 + ln, cy = ry0 + c - COFF;
+            const bool cok = c < ccol && cy >= 0 && cy < P.W;
+#pragma unroll
+            for (int k = 0; k < KR; ++k) {
+                const int r = wv + 16 * k, cx = rx0 + r - COFF;
+                cv[j * KR + k] = 255;
+                if (j * 64 < ccol && r < crow && cx >= 0 && cx < P.L && cok) cv[j * KR + k] = cbase[(size_t)cx * P.W + cy];
+            }
+        }
+        constexpr int CPT = TT / 256, KT = RTMAX * RTMAX * CPT / 16;                 // CPT: 64-lane float4 pieces per tile
+        float4 gv[KT];
+        unsigned int bv[KT];
+#pragma unroll
+        for (int k = 0; k < KT; ++k) {
+            const int pc = wv + 16 * k, tl = pc / CPT;
+            if (tl >= ntl) continue;
+            const int ti = region_tile_row(tl, nty_magic), tj = tl - ti * J.nty, v = (pc - tl * CPT) * 64 + ln;
+            const size_t gt = (size_t)(gt0 + (J.tx0 + ti) * P.TY + J.ty0 + tj);
+            gv[k] = reinterpret_cast<const float4 *>(P.G + gt * TT)[v];
+            bv[k] = reinterpret_cast<const unsigned int *>(P.bp + gt * TT)[v];
+        }
+        // the frame (at most 4 * RN + 4 elements: one per thread)
+        static_assert(4 * RN + 4 <= NTHR, "one frame element per thread");
+        float fv = INFINITY;
+        int fo = -1;
+        // (region_frame_at(tid, rnx, rny) of ufm_region_rect.h, written out: through the function -- even through region_frame_count alone -- the lean
+        //  FD form spills eight more scalar registers here, where every load of the prologue is in flight.  The driver walks the function for these sizes.)
+        if (tid < 2 * (rny + 2) + 2 * rnx) {
+            int hx, hy;
+            if (tid < rny + 2) { hx = -1; hy = tid - 1; }
+            else if (tid < 2 * (rny + 2)) { hx = rnx; hy = tid - (rny + 2) - 1; }
+            else if (tid < 2 * (rny + 2) + rnx) { hx = tid - 2 * (rny + 2); hy = -1; }
+            else { hx = tid - 2 * (rny + 2) - rnx; hy = rny; }
+            const int x = rx0 + hx, y = ry0 + hy;
+            fo = region_field_offset(hx, hy);
+            if (x >= 0 && y >= 0 && x < P.TX * T && y < P.TY * T) fv = P.G[gaddr(P, m, x, y)];
+        }
+        STAMP(7);
+#pragma unroll
+        for (int j = 0; j < KP; ++j) {
+            const int c = j * 64 + ln;
+#pragma unroll
+            for (int k = 0; k < KR; ++k) {
+                const int r = wv + 16 * k;
+                if (j * 64 < ccol && r < crow && c < ccol) Cb[r * RCP + c] = cv[j * KR + k];
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < KT; ++k) {
+            const int pc = wv + 16 * k, tl = pc / CPT;
+            if (tl >= ntl) continue;
+            const int ti = region_tile_row(tl, nty_magic), tj = tl - ti * J.nty, e = ((pc - tl * CPT) * 64 + ln) * 4;
+            float *g = &Gs[(ti * T + e / T + 1) * RP + tj * T + e % T + 1];
+            g[0] = gv[k].x; g[1] = gv[k].y; g[2] = gv[k].z; g[3] = gv[k].w;
+            *reinterpret_cast<unsigned int *>(&Bb[(ti * T + e / T) * RBP + tj * T + e % T]) = bv[k];
+        }
+        if (fo >= 0) Gs[fo] = fv;
+    }
+    region_apply_patches<CELLS, DBG>(P, J, B, r_first, one_fused, pb0);      // 0b (ends behind a barrier if it seeded)
+    STAMP(4);
+    // ---- 0c. what k_replan_begin does: step bookkeeping, mark reset, the seeds, the invalidation bound ----
+    if (tid == 0 && !J.batch) *P.dyn = J.dyn;      // (a batch: the host has put them in place before the launch -- other workgroups read them too)
+    if (!J.batch) step_begin(P, J.rb.sb);
+    if (!one_fused)
+        for (int r = 0; r < J.rb.nrect; ++r) {
+            const int *qr = J.rb.rect[r];
+            for (int e = tid; e < (qr[3] + 1) * (qr[4] + 1); e += NTHR) clear_mark(P, qr[0], qr[1], qr[2], qr[3], qr[4], e);
+        }
+    for (int i = tid; i < (int)(sizeof(RegionShared) / sizeof(int)); i += NTHR) reinterpret_cast<int *>(&S)[i] = 0;
+    __syncthreads();
+    STAMP(5);
+    for (int i = tid; i < 2 * RTMAX * RTMAX; i += NTHR) (&S.dprio[0][0])[i] = INFBITS;
+    for (int i = tid; i < RFRAME; i += NTHR) { S.actL[i] = INFBITS; S.actR[i] = INFBITS; }
+    for (int i = tid; i < 16 * RWW * 32; i += NTHR) (&S.pkey[0][0])[i] = INFBITS;
+    if (tid == 0) { S.rmin = INFBITS; S.m_r = INFBITS; }
+    {   // pending seeds of this map (all consumed): tiles inside the block are handled here, any other goes to the queue
+        // (n_pending was read before the patches of this job were seeded: the general seeding above appends to the list)
+        const int n = one_fused ? n_pending : P.ctr->scount;
+        for (int i = tid; i < n; i += NTHR) {
+            const int gt = P.slist[i];
+            if (gt / P.NTm != m) continue;
+            const int tx = (gt - gt0) / P.TY, ty = (gt - gt0) - tx * P.TY;
+            P.sflag[gt] = 0;
+            if (tx < J.tx0 || tx >= J.tx0 + J.ntx || ty < J.ty0 || ty >= J.ty0 + J.nty) activate(P, Q_RAISE, J.rb.k_raise, gt, 0);
+        }
+        __syncthreads();
+        STAMP(6);
+        if (tid == 0 && !J.batch) { P.ctr->scount = 0; P.ctr->done = 0; }   // (a batch: the last workgroup, when everybody has read the list)
+        if (tid < 64) {
+            // the start's key before the patch (start_bound(), from the values asked for at the top): one start element per lane 0..3 (one thread
+            // after the other -- four divisions, four hypotf -- this was a microsecond in front of the phases), the largest key by two shuffles
+            float key = 0.0f, dist = 0.0f;
+            int off = -1;
+            if (se_x >= 0) {
+                if (HEUR) dist = hm * hypotf(J.rb.sb.sx - (float)se_x, J.rb.sb.sy - (float)se_y);
+                if (sg < INFINITY) key = sg + dist;
+                if (se_x >= rx0 && se_x < rx0 + rnx && se_y >= ry0 && se_y < ry0 + rny) off = (se_x - rx0 + 1) * RP + (se_y - ry0 + 1);
+            }
+            if (tid < 4) { S.soff[tid] = off; S.sdist[tid] = dist; }
+            const bool in = __builtin_amdgcn_ballot_w64(off >= 0) != 0ull;
+            float b0 = fmaxf(key, __shfl_xor(key, 1));
+            b0 = fmaxf(b0, __shfl_xor(b0, 2));
+            if (tid == 0) {
+                b0 = b0 > 0.0f ? b0 : INFINITY;
+                S.B0 = b0;
+                S.rbound = focused ? b0 + J.rb.band : INFINITY;
+                S.any_start_in = in ? 1 : 0;
+            }
+        }
+    }
+
+    if (DBG && tid == 0) { S.tstamp[0] = t_begin; S.tstamp[1] = wall_clock64(); S.tstamp[2] = S.tstamp[1]; }
+    __syncthreads();
+    region_seed_wake<CELLS>(J, B);
+    __syncthreads();
+    const int goal_lx = goal_x - rx0, goal_ly = goal_y - ry0;
+
+    // ---- 2. invalidate, lower; again while an invalidation that was held back lies below the start's new key ----
+    for (int round = 0;; ++round) {
+        for (;;) {
+            region_phase<ALGOF, MODE_RAISE, FORM>(P, J, Gs, Cb, Bb, S, thr, hm, focused, goal_lx, goal_ly);
+            // a tile that lost a value after some of its patches had been held back: those patches again
+            const int again_t = __syncthreads_or(tid < ntl && S.traised[tid] && S.dprio[1][tid] != INFBITS) && !S.giveup;
+            __syncthreads();
+            if (!again_t) break;
+            region_reopen<false>(S, 1);
+            __syncthreads();
+        }
+        if (DBG && tid == 0 && round == 0) S.tstamp[3] = wall_clock64();
+        // everything the invalidation swept is re-lowered (plus, in later rounds, what lowering had to hold back)
+        region_reopen<true>(S, 0);
+        if (tid == 0) {
+            S.dkey = INFBITS;
+            S.Bsub = focused ? region_lower_bound(Gs, S) : INFINITY;
+            // the first band: everything below the smallest value that was taken away, plus one band width (a step without
+            // invalidations is not ordered: its few lowered values sit around the patch)
+            S.theta = (round == 0) ? ((S.rmin != INFBITS) ? __int_as_float(S.rmin) + J.delta : INFINITY) : S.theta;
+            S.Bgate = fminf(S.Bsub + J.slack, S.theta);
+        }
+        __syncthreads();
+        for (int sub = 0;; ++sub) {
+            region_phase<ALGO, MODE_LOWER, FORM>(P, J, Gs, Cb, Bb, S, thr, hm, focused, goal_lx, goal_ly);
+            // the smallest key the sub-round leaves held back: over the patches' last bursts (S.pkey)
+            for (int i = tid; i < 16 * RWW * 32; i += NTHR) { const int k = (&S.pkey[0][0])[i]; if (k != INFBITS) atomicMin(&S.dkey, k); }
+            __syncthreads();
+            // the start's key may have risen while results were being held back against an earlier value of it
+            if (tid == 0) {
+                const float B = focused ? region_lower_bound(Gs, S) : INFINITY;
+                const int m = S.dkey;
+                bool again = !S.giveup && m != INFBITS && (__int_as_float(m) < B || B == INFINITY);
+                if (again && sub >= 4096) { again = false; S.giveup = 1; }   // (never seen; what is dirty goes to the queues)
+                S.again = again ? 1 : 0;
+                S.Bsub = B;
+                if (again) S.theta = fmaxf(S.theta, __int_as_float(m)) + J.delta;    // the next band starts where work is waiting
+                S.Bgate = fminf(S.Bsub + J.slack, S.theta);
+            }
+            __syncthreads();
+            const int again_l = S.again;
+            __syncthreads();                    // (thread 0 overwrites the word below: everyone has read it first)
+            if (!again_l) break;
+            if (DBG && tid == 0) ++S.dbg[2];
+            region_reopen<false>(S, 0);
+            if (tid == 0) S.dkey = INFBITS;
+            __syncthreads();
+        }
+        if (tid < ntl && S.dprio[1][tid] != INFBITS) atomicMin(&S.m_r, S.dprio[1][tid]);     // (S.m_r: INFBITS here, reset below)
+        __syncthreads();
+        if (tid == 0) {
+            const float B = focused ? region_lower_bound(Gs, S) : INFINITY;
+            const int m = S.m_r;
+            S.m_r = INFBITS;
+            bool again = !S.giveup && focused && m != INFBITS && __int_as_float(m) < B + J.slack;   // lowering reaches the key plus one move
+            if (again && round >= 14) { again = false; S.giveup = 1; }
+            if (again) S.rbound = fmaxf(B, S.rbound) + J.rb.band;
+            S.again = again ? 1 : 0;
+        }
+        __syncthreads();
+        const int again_r = S.again;
+        __syncthreads();
+        if (!again_r) break;
+        if (DBG && tid == 0) ++S.dbg[3];
+        region_reopen<false>(S, 1);
+        __syncthreads();
+    }
+
+    if (DBG && tid == 0) S.tstamp[4] = wall_clock64();
+    static_assert(NTHR == 1024 && TT % 64 == 0 && RBP % 4 == 0, "the block kernel deals its staging and write-back out by wave");
+    constexpr int UPT = REGION_UPT;                                     // units (64 consecutive elements = one wave) per tile
+    const int wvw = __builtin_amdgcn_readfirstlane(tid >> 6), lnw = tid & 63;
+    auto unit_tile = [&](int u, int &k, int &part, int &tl, int &ti, int &tj) {      // (all wave-uniform)
+        region_unit(u, k, part); tl = __builtin_amdgcn_readfirstlane(s_wbl[k]);
+        ti = region_tile_row(tl, nty_magic); tj = tl - ti * J.nty;
+    };
+    // ---- 3. write back: changed values, the rings of the neighbours they border, what the frame has to hear ----
+    // frame tile index of the tile at block coordinates (ti, tj), ti in -1..ntx, tj in -1..nty (one of them outside)
+    auto frame_index = [&](int ti, int tj) { return region_frame_index(ti, tj, J.ntx, J.nty); };
+    // (Round 4: this used to be two loops of 16 iterations per thread over ALL tiles of the largest block, unrolled so that the values HBM holds could wait in
+    //  registers between them -- 12 000 instructions of which a replan executes a sixth, fetched cold at every launch.  Now: the tiles that have something to
+    //  write are listed, what HBM holds of them goes straight into LDS (no register held, every load in flight at once), and one loop walks the list.)
+    if (tid < 64) {
+        const bool has = tid < ntl && S.tflag[tid];      // (the tiles that only hold renewed back-pointers: the tail's list, behind the flag)
+        const unsigned long long hm_ = __builtin_amdgcn_ballot_w64(has);
+        if (has) s_wbl[__popcll(hm_ & ((1ull << tid) - 1ull))] = tid;
+        if (tid == 0) s_nwb = __popcll(hm_);
+    }
+    __syncthreads();
+    const int nunits = s_nwb * UPT;
+    {
+        typedef __attribute__((address_space(3))) void *lds_ptr;
+        typedef const __attribute__((address_space(1))) void *glb_ptr;
+#pragma unroll 1
+        for (int u = wvw; u < nunits; u += 16) {
+            int k, part, tl, ti, tj;
+            unit_tile(u, k, part, tl, ti, tj);
+            if (k >= NG0) continue;
+            const size_t gt = (size_t)(gt0 + (J.tx0 + ti) * P.TY + J.ty0 + tj);
+            __builtin_amdgcn_global_load_lds((glb_ptr)(P.G + gt * TT + part * 64 + lnw), (lds_ptr)(G0c + k * TT + part * 64), 4, 0, 0);
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    __syncthreads();
+    int n_exp = 0;
+#pragma unroll 1
+    for (int u = wvw; u < nunits; u += 16) {
+        int k, part, tl, ti, tj;
+        unit_tile(u, k, part, tl, ti, tj);
+        const int e = part * 64 + lnw;
+        const int tx = J.tx0 + ti, ty = J.ty0 + tj, gt = gt0 + tx * P.TY + ty;
+        const int io_r = e / T, io_c = e % T;
+        float gl0;
+        if (k < NG0) gl0 = G0c[k * TT + e];
+        else { gl0 = P.G[(size_t)gt * TT + e]; P.Gprev[(size_t)gt * TT + e] = gl0; }      // (more changed tiles than the LDS copy holds: their old values go to the snapshot at once)
+        const float gf = Gs[(ti * T + io_r + 1) * RP + tj * T + io_c + 1];
+        if (gf == gl0) continue;
+        ++n_exp;
+        P.G[(size_t)gt * TT + e] = gf;
+        const int er = (io_r == 0) ? -1 : ((io_r == T - 1) ? 1 : 0);
+        const int ec = (io_c == 0) ? -1 : ((io_c == T - 1) ? 1 : 0);
+        const bool rok = er && tx + er >= 0 && tx + er < P.TX, cok = ec && ty + ec >= 0 && ty + ec < P.TY;
+        if (rok) P.ring[(size_t)(gt + er * P.TY) * RING + (er < 0 ? RING_BOT : RING_TOP) + io_c] = gf;
+        if (cok) P.ring[(size_t)(gt + ec) * RING + (ec < 0 ? RING_RIGHT : RING_LEFT) + io_r] = gf;
+        if (rok && cok) P.ring[(size_t)(gt + er * P.TY + ec) * RING + RING_CORNER + (er < 0 ? 2 : 0) + (ec < 0 ? 1 : 0)] = gf;
+        // neighbours outside the block: lowered value -> lowering queue, lost / raised value -> invalidation queue,
+        // each only if an element of that neighbour (the frame, as staged) can be concerned at all (causality, see k_relax)
+        const bool out_r = rok && (ti + er < 0 || ti + er >= J.ntx), out_c = cok && (tj + ec < 0 || tj + ec >= J.nty);
+        if (!(out_r || out_c)) continue;
+        const int lxr = ti * T + io_r + 1, lyc = tj * T + io_c + 1;          // position in Gs
+        const int cl = max(io_c - 1, 0) - io_c, ch = min(io_c + 1, T - 1) - io_c;   // columns / rows of the edge neighbour itself
+        const int rl = max(io_r - 1, 0) - io_r, rh = min(io_r + 1, T - 1) - io_r;
+        const float lo = fminf(gf, gl0);
+        const bool lowered = gf < gl0;
+        const int pb = __float_as_int(lowered ? gf : gl0);
+        auto concerned = [&](float a, float b, float c) {
+            if (lowered) return lo < fmaxf(fmaxf(a, b), c);                  // someone above the new value
+            const float fa = a < INFINITY ? a : -INFINITY, fb = b < INFINITY ? b : -INFINITY, fc = c < INFINITY ? c : -INFINITY;
+            return gl0 < fmaxf(fmaxf(fa, fb), fc);                          // someone (finite) above the old value may have leaned on it
+        };
+        if (out_r) {
+            const float *h = Gs + (lxr + er) * RP + lyc;
+            if (concerned(h[cl], h[0], h[ch])) atomicMin(lowered ? &S.actL[frame_index(ti + er, tj)] : &S.actR[frame_index(ti + er, tj)], pb);
+        }
+        if (out_c) {
+            const float *h = Gs + lxr * RP + lyc + ec;
+            if (concerned(h[rl * RP], h[0], h[rh * RP])) atomicMin(lowered ? &S.actL[frame_index(ti, tj + ec)] : &S.actR[frame_index(ti, tj + ec)], pb);
+        }
+        if (rok && cok && (out_r || out_c)) {                               // the diagonal neighbour
+            const int di = ti + er, dj = tj + ec;
+            if (di < 0 || di >= J.ntx || dj < 0 || dj >= J.nty) {
+                const float hv = Gs[(lxr + er) * RP + lyc + ec];
+                if (concerned(hv, hv, hv)) atomicMin(lowered ? &S.actL[frame_index(di, dj)] : &S.actR[frame_index(di, dj)], pb);
+            }
+        }
+    }
+    if (n_exp) atomicAdd(&S.expanded, n_exp);
+    __syncthreads();
+    region_hand_over(P, J, B);
+    // (one workgroup of a batch reads what another one queued: agent scope; a single map's end check only reads what this very
+    //  workgroup wrote -- its loads are agent-scope loads from the XCD's L2, where its stores are once they have been acknowledged)
+    if (J.batch) __threadfence(); else __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __syncthreads();
+
+    if (DBG && tid == 0) S.tstamp[5] = wall_clock64();
+    region_end_check<DBG>(P, J, B, focused);                    // 4
+    // not done: the launch chain takes over; the tiles changed here join the step's touched list with their values
+    // as of the start of the step (num_nodes_expanded is counted against that snapshot at the end of the step)
+    if (!S.done) {
+#pragma unroll 1
+        for (int u = wvw; u < nunits; u += 16) {
+            int k, part, tl, ti, tj;
+            unit_tile(u, k, part, tl, ti, tj);
+            const int e = part * 64 + lnw;
+            const int gt = gt0 + (J.tx0 + ti) * P.TY + J.ty0 + tj;
+            if (k < NG0) P.Gprev[(size_t)gt * TT + e] = G0c[k * TT + e];
+            if (e == 0) {
+                P.fresh[gt] = 0;
+                if (atomicAdd(&P.touched[gt], 1) == 0) P.tlist[atomicAdd(&P.ctr->tcount, 1)] = gt;
+            }
+        }
+    }
+    if (J.batch) __threadfence();          // (a single map: the kernel's end, or thread 0's system-scope release below, publishes)
+    __syncthreads();
+    region_publish<DBG>(P, J, B, host, flag, s_last);           // 5
 
     // ---- 6. the tail, behind the flag: the back-pointers (what k_finalize_bp does for the launch chain's steps).  Every node of a patch in
     // which a value changed, and of the patches around it -- a neighbour's value may be what it was and still come from another triangle
@@ -979,7 +1017,7 @@ __global__ __launch_bounds__(NTHR) void k_replan_region(DevParams P, RegionJobs 
                 const int j = __ffs(bits) - 1;
                 bits &= bits - 1;
                 const int idx = wd * 32 + j;
-                const int pr = (idx / RPW) * 4 + (w >> 2), pc = (idx % RPW) * 4 + (w & 3);
+                const int pr = region_bit_row(w, idx), pc = region_bit_col(w, idx);
                 if (pr >= nprow || pc >= npcol) continue;
                 const int lx = pr * 4 + (nd >> 2), ly = pc * 4 + (nd & 3);
                 QuadConsts<ALGO> C;
@@ -1015,4 +1053,5 @@ __global__ __launch_bounds__(NTHR) void k_replan_region(DevParams P, RegionJobs 
         __syncthreads();
         if (tid == 0) P.lmax[38] = (int)(wall_clock64() - S.tstamp[0]);
     }
+#undef STAMP
 }
