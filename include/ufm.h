@@ -511,6 +511,10 @@ int ufm_batch_extract_path(ufm_batch_t *b, int max_steps, int lookahead, int all
 int ufm_batch_extract_paths_from(ufm_batch_t *b, int n_starts, const int32_t *map_index, const float *starts_xy, int max_steps,
                                  int lookahead, int allow_indirect, float *path_xy, int cap_points, float *step_costs, int cap_costs,
                                  ufm_path_info *info);
+/* ---- trajectory scoring: what the caller's polylines cost on the planning raster, and whether they are blocked -- ufm_score, the two
+ * calls of a planner and the two of a batch.  The contract and the declarations are a header of their own, included here: whoever
+ * includes ufm.h has them. ---- */
+#include "ufm_score.h"
 
 #ifdef __cplusplus
 }

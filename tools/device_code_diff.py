@@ -2,7 +2,9 @@
 
 `make -C unige-tasi-path-planners_amd device-asm [DEFS="-D..."] ASM=A.s` writes one.  A refactor that must not move the kernels is held to this:
 the same function names on both sides and every body the same text.  Text only -- the comparison knows nothing about instructions.  The one line of
-a device assembly that follows the SOURCE text rather than the code, the module's __hip_cuid_<hash> symbol, is ignored.
+a device assembly that follows the SOURCE text rather than the code, the module's __hip_cuid_<hash> symbol, is ignored; so is the number a
+local label carries for its function's POSITION in the module (.LBB46_2, .Lfunc_end46, .LJTI46_0 -> .LBB#_2 ...): a kernel added in front of
+another moves that number and nothing else of the other's body.
 Prints the counts, the names present on one side only and the names whose bodies differ; --show N prints the first N differing lines of each.
 Exit status 0: no difference."""
 import argparse
@@ -11,13 +13,14 @@ import re
 import sys
 
 CUID = re.compile(r"__hip_cuid_[0-9a-f]+")
+ORDINAL = re.compile(r"(?<![A-Za-z0-9_])((?:\.L)?(?:BB|JTI|func_begin|func_end))\d+")      # (also the "Header=BB46_3" of a comment)
 
 
 def functions(path):
     """{name: [body lines]} for every function of a device assembly (a .type NAME,@function line ... its .Lfunc_end label), and the other lines"""
     funcs, rest, name = {}, [], None
     for line in open(path):
-        line = CUID.sub("__hip_cuid_", line.rstrip("\n"))
+        line = ORDINAL.sub(r"\1#", CUID.sub("__hip_cuid_", line.rstrip("\n")))
         m = re.match(r"\s*\.type\s+(\S+),@function", line)
         if m:
             name = m.group(1)

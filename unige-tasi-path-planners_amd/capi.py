@@ -60,6 +60,24 @@ class PathInfo(C.Structure):
     ]
 
 
+# ufm_score (include/ufm_score.h): the record of one scored path, as score_paths returns it
+SCORE_DTYPE = np.dtype([("cost", "<f4"), ("cost_before", "<f4"), ("dist", "<f4"), ("blocked_at", "<f4"),
+                        ("blocked_segment", "<i4"), ("pieces", "<i4")])
+
+
+def _path_arrays(paths):
+    """(points float32 [total, 2], offsets int32 [n + 1]) of `paths`: a list of [n_i, 2] arrays, or the pair (points, offsets) itself"""
+    if isinstance(paths, tuple) and len(paths) == 2 and np.ndim(paths[1]) == 1 and np.ndim(paths[0]) == 2:
+        pts, off = paths
+        return np.ascontiguousarray(pts, np.float32).reshape(-1, 2), np.ascontiguousarray(off, np.int32)
+    parts = [np.asarray(p, np.float32).reshape(-1, 2) for p in paths]
+    off = np.zeros(len(parts) + 1, np.int32)
+    if parts:
+        off[1:] = np.cumsum([len(p) for p in parts])
+    pts = np.concatenate(parts) if parts else np.zeros((0, 2), np.float32)
+    return np.ascontiguousarray(pts, np.float32), off
+
+
 # The surface, once: (operation, forms, argument types after the handle and the map index).  Forms: "p" ufm_<op>(planner, ...);
 # "b" ufm_batch_<op>(batch, ...); "B" ufm_batch_<op>(batch, map index, ...); "f" ufm_<op>(...), no handle.  An operation whose two
 # forms take different arguments has a row for each.  SYMBOLS, every argtypes and every restype come from here.
@@ -99,6 +117,15 @@ _RESTYPE = {"version": C.c_char_p, "stream": _vp}       # everything else return
 _FORMS = {"p": ("ufm_", [_vp]), "b": ("ufm_batch_", [_vp]), "B": ("ufm_batch_", [_vp, _i]), "f": ("ufm_", [])}
 # every symbol include/ufm.h declares (checked by tests/test_capi_symbols.py)
 SYMBOLS = [_FORMS[form][0] + op for op, forms, _ in _OPS for form in forms]
+# Trajectory scoring is a header of its own, include/ufm_score.h, which ufm.h includes (ufm.h's own list of entry points is held to a
+# fixed count by tests/test_capi_surface.py): its rows, in the same format, bound by the same loop; SCORE_SYMBOLS is what it declares
+# (checked by tests/test_score_surface.py).  A second table is debt: whoever may next change that count folds these rows into _OPS and
+# the declarations into ufm.h.
+_SCORE_OPS = [
+    ("score_paths", "p", [_i, _vp, _vp, _vp]), ("score_paths", "b", [_i, _vp, _vp, _vp, _vp]),
+    ("score_paths_device", "pB", [_i, _i, _vp, _vp, _vp]),
+]
+SCORE_SYMBOLS = [_FORMS[form][0] + op for op, forms, _ in _SCORE_OPS for form in forms]
 
 _LIB_PATH = os.path.join(_HERE, "libufm.so")
 
@@ -131,7 +158,7 @@ def load_library():
                        "or __graft_entry__.build()); there is no CPU fallback")
     L = C.CDLL(so)
     fn = {kind: types.SimpleNamespace() for kind in "pbf"}
-    for op, forms, args in _OPS:
+    for op, forms, args in _OPS + _SCORE_OPS:
         for form in forms:
             prefix, head = _FORMS[form]
             func = getattr(L, prefix + op)
@@ -322,6 +349,19 @@ class _Handle:
         return [(pts[k, :info[k].n_points].copy(), costs[k, :info[k].n_costs].copy(),
                  info[k].total_cost, info[k].total_dist) for k in range(n)], info
 
+    def _score(self, paths, pre=()):
+        """score_paths of both classes (ufm_score_paths / ufm_batch_score_paths; `pre`: a batch's map indices): one SCORE_DTYPE record
+        per path, in the caller's order"""
+        pts, off = _path_arrays(paths)
+        n = len(off) - 1
+        out = np.zeros(max(n, 1), SCORE_DTYPE)
+        keep = np.zeros((1, 2), np.float32) if len(pts) == 0 else pts        # (an address even when no path has a point)
+        _call(self._F.score_paths, self.h, n, *pre, off.ctypes.data, keep.ctypes.data, out.ctypes.data)
+        return out[:n]
+
+    def _score_device(self, at, n_paths, total_points, dev_offsets, dev_points, dev_out):
+        _call(self._F.score_paths_device, self.h, *at, int(n_paths), int(total_points), dev_offsets, dev_points, dev_out)
+
     # ---- one map: `at` ----
     def _raster_set(self, at, op, raster, width, length, *more):
         """set_map / set_survey / set_layer ...: ufm_<op> or ufm_<op>_device by where the raster lives"""
@@ -482,6 +522,17 @@ class Planner(_Handle):
         starts = np.ascontiguousarray(starts, np.float32).reshape(-1, 2)
         out, self.path_infos = self._extract(len(starts), max_steps, lookahead, allow_indirect, (len(starts), starts.ctypes.data))
         return out
+
+    def score_paths(self, paths):
+        """trajectory scoring (ufm_score_paths): what the caller's polylines cost on the planning raster, and whether they are blocked.
+        `paths`: a list of [n_i, 2] arrays of (x, y), or (points [total, 2], offsets [n + 1]).  Returns a structured array
+        (SCORE_DTYPE: cost, cost_before, dist, blocked_at, blocked_segment, pieces), one record per path.  Read-only on the planner."""
+        return self._score(paths)
+
+    def score_paths_device(self, n_paths, total_points, dev_offsets, dev_points, dev_out):
+        """ufm_score_paths_device: offsets (int32 [n_paths + 1]), points (float32 [total_points, 2]) and records (ufm_score [n_paths])
+        as device addresses, e.g. tensor.data_ptr(); queued on the engine's stream (stream_ptr()), nothing is waited for"""
+        self._score_device((), n_paths, total_points, dev_offsets, dev_points, dev_out)
 
     def read_map(self, width, length):
         return self._raster_read((), "read_map", width, length)
@@ -666,6 +717,18 @@ class BatchPlanner(_Handle):
         assert len(mi) == len(starts), "one map index per start"
         out, self.path_infos = self._extract(len(starts), max_steps, lookahead, allow_indirect, (len(starts), mi.ctypes.data, starts.ctypes.data))
         return out
+
+    def score_paths(self, map_index, paths):
+        """as Planner.score_paths: path k lies on map map_index[k] (any order, any number per map)"""
+        mi = np.ascontiguousarray(map_index, np.int32).ravel()
+        pts, off = _path_arrays(paths)
+        if len(mi) != len(off) - 1:
+            raise UfmError("one map index per path")
+        return self._score((pts, off), (mi.ctypes.data,))
+
+    def score_paths_device(self, i, n_paths, total_points, dev_offsets, dev_points, dev_out):
+        """as Planner.score_paths_device: every path on map i, the buffers on that map's device, queued on its shard's stream"""
+        self._score_device((int(i),), n_paths, total_points, dev_offsets, dev_points, dev_out)
 
     def read_field(self, i):
         return self._read_field((i,), 0, 0, *self._dims, False)[0]

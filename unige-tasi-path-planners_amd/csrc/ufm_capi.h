@@ -5,7 +5,7 @@
 // forward to ufm_batch_X with map 0, and the batch form is the only one with a body.  Calls that exist for a planner alone
 // (ufm_field_dims, ufm_read_info*, ufm_read_queue, ufm_debug_*) use shard 0, map 0 of the same handle.  Where the two forms differ
 // (DESIGN.md section 2.1): ufm_reveal refuses row < 0, which a batch reads as "skip this map"; ufm_extract_paths_from takes no map
-// indices, which ufm_batch_extract_paths_from requires.
+// indices, which ufm_batch_extract_paths_from requires; likewise ufm_score_paths and ufm_batch_score_paths.
 #pragma once
 
 struct ufm_batch { std::vector<Engine *> shards; int n_maps = 0, per = 1; };
@@ -423,6 +423,25 @@ int ufm_batch_extract_paths_from(ufm_batch_t *b, int n_starts, const int32_t *ma
 int ufm_extract_paths_from(ufm_t *p, int n_starts, const float *starts_xy, int max_steps, int lookahead, int allow_indirect,
                            float *path_xy, int cap_points, float *step_costs, int cap_costs, ufm_path_info *info) {
     return batch_paths_from(p, n_starts, nullptr, starts_xy, max_steps, lookahead, allow_indirect, path_xy, cap_points, step_costs, cap_costs, info);
+}
+// trajectory scoring: path k lies on map map_index[k]; a planner has one map and passes no indices
+static int batch_score_paths(ufm_batch *b, int n_paths, const int32_t *map_index, const int32_t *offsets, const float *points_xy, ufm_score *out) {
+    if (!b || b->shards.empty()) return UFM_ERR_INVALID;
+    return score_paths(b->shards.data(), b->per, b->n_maps, n_paths, map_index, offsets, points_xy, out);
+}
+int ufm_batch_score_paths(ufm_batch_t *b, int n_paths, const int32_t *map_index, const int32_t *offsets, const float *points_xy, ufm_score *out) {
+    if (!map_index) return UFM_ERR_INVALID;
+    return batch_score_paths(b, n_paths, map_index, offsets, points_xy, out);
+}
+int ufm_score_paths(ufm_t *p, int n_paths, const int32_t *offsets, const float *points_xy, ufm_score *out) {
+    return batch_score_paths(p, n_paths, nullptr, offsets, points_xy, out);
+}
+int ufm_batch_score_paths_device(ufm_batch_t *b, int i, int n_paths, int total_points, const int32_t *dev_offsets, const float *dev_points_xy, ufm_score *dev_out) {
+    UFM_BATCH_MAP(b, i);
+    return engine_score_device(e, li, n_paths, total_points, dev_offsets, dev_points_xy, dev_out);
+}
+int ufm_score_paths_device(ufm_t *p, int n_paths, int total_points, const int32_t *dev_offsets, const float *dev_points_xy, ufm_score *dev_out) {
+    return ufm_batch_score_paths_device(p, 0, n_paths, total_points, dev_offsets, dev_points_xy, dev_out);
 }
 
 // ---- a planner alone: shard 0, map 0 ----

@@ -15,6 +15,7 @@
 #include "ufm_route.h"
 #include "ufm_patch_route.h"
 #include "ufm_path.h"
+#include "ufm_score.h"
 
 static_assert(RJOBS <= ROUTE_MAX_JOBS && RTMAX >= 3, "ufm_route.h places at most ROUTE_MAX_JOBS blocks");
 constexpr RouteConfig ROUTE_CONFIG{T, RTMAX, RJOBS, ROUTE_MAX_RECTS, 65 * 65};
@@ -133,6 +134,11 @@ struct Engine : Knobs {     // the tuning members -- what ufm_set_param sets -- 
     GrowArray<int32_t> d_info;       // ufm_read_info: back-pointers of the requested window
     GrowArray<PathJob> d_jobs;       // path extraction: the walks of one launch, with the pinned twin
     GrowArray<float> d_path;         // ... and the per-job output records, with the pinned twin
+    struct ScoreStage {              // trajectory scoring, the host forms: one launch's paths and records, each with its pinned twin
+        GrowArray<int32_t> idx;      // [cnt + 1] offsets into pts, then [cnt] map indices
+        GrowArray<float> pts;        // the points of the launch's paths, dense
+        GrowArray<ufm_score> out;    // [cnt]
+    } score;
     std::vector<MapState> maps;
     std::vector<PatchRect> pending;
     int iter[2] = {0, 0};            // index k of the next relax launch of each queue (never reset: the queues persist)
@@ -1322,6 +1328,82 @@ int paths_from(Engine *const *shards, int per, int n_maps, int n_starts, const i
     }
     const float ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     for (int k = 0; k < n_starts; ++k) info[k].e_ms = ms;
+    return UFM_OK;
+}
+
+// Trajectory scoring (ufm_score_paths ...; k_score_paths, ufm_score.h): n of the caller's paths on this engine's maps, one wavefront
+// each.  Path q[j].k of the caller's arrays -- points offsets[k] .. offsets[k + 1] - 1 of points_xy -- lies on map q[j].m and its record
+// goes to out[k].  The caller has checked the arguments; patches that are being held are applied first (the walk reads the raster).
+// Launches of at most SCORE_CHUNK_PATHS paths, each staged dense through the pinned twins and followed by a wait for the stream.
+struct ScoreQuery { int m; size_t k; };
+constexpr size_t SCORE_CHUNK_PATHS = 65536;
+int engine_score(Engine *e, const ScoreQuery *q, size_t n, const int32_t *offsets, const float *points_xy, ufm_score *out) {
+    HIPCHK(hipSetDevice(e->device));
+    { int rc = e->flush_deferred(); if (rc != UFM_OK) return rc; }
+    const PathField F = path_field(e, 0);     // (the paths name their maps)
+    Engine::ScoreStage &st = e->score;
+    for (size_t first = 0; first < n; first += SCORE_CHUNK_PATHS) {
+        const size_t cnt = std::min(SCORE_CHUNK_PATHS, n - first);
+        size_t npts = 0;
+        for (size_t j = 0; j < cnt; ++j) { const size_t k = q[first + j].k; npts += (size_t)(offsets[k + 1] - offsets[k]); }
+        if (npts > (size_t)INT_MAX) return UFM_ERR_INVALID;
+        // (the pinned twins are free: every chunk ends with a wait for the stream)
+        { int rc = st.idx.reserve(e->stream, 2 * cnt + 1, true, true); if (rc != UFM_OK) return rc; }
+        { int rc = st.pts.reserve(e->stream, 2 * std::max<size_t>(npts, 1), true, true); if (rc != UFM_OK) return rc; }
+        { int rc = st.out.reserve(e->stream, cnt, true, true); if (rc != UFM_OK) return rc; }
+        int32_t *h_off = st.idx.pinned, *h_map = h_off + cnt + 1;
+        size_t at = 0;
+        for (size_t j = 0; j < cnt; ++j) {
+            const size_t k = q[first + j].k, np = (size_t)(offsets[k + 1] - offsets[k]);
+            h_off[j] = (int32_t)at;
+            h_map[j] = q[first + j].m;
+            if (np) std::memcpy(st.pts.pinned + 2 * at, points_xy + 2 * (size_t)offsets[k], sizeof(float) * 2 * np);
+            at += np;
+        }
+        h_off[cnt] = (int32_t)at;
+        HIPCHK(hipMemcpyAsync(st.idx, st.idx.pinned, sizeof(int32_t) * (2 * cnt + 1), hipMemcpyHostToDevice, e->stream));
+        if (npts) HIPCHK(hipMemcpyAsync(st.pts, st.pts.pinned, sizeof(float) * 2 * npts, hipMemcpyHostToDevice, e->stream));
+        k_score_paths<<<(unsigned)cnt, 64, 0, e->stream>>>(F, e->P.cstride, st.idx, st.idx + cnt + 1, 0, st.pts, (int)npts, st.out);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(st.out.pinned, st.out, sizeof(ufm_score) * cnt, hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));
+        for (size_t j = 0; j < cnt; ++j) out[q[first + j].k] = st.out.pinned[j];
+    }
+    return UFM_OK;
+}
+
+// The host forms (ufm_score_paths / ufm_batch_score_paths): path k lies on map map_index[k] (nullptr: map 0) of the handle, whose map i
+// lives in shards[i / per].  Everything is checked before anything is launched or written; one launch sequence per shard, records in
+// the caller's order.
+int score_paths(Engine *const *shards, int per, int n_maps, int n_paths, const int32_t *map_index, const int32_t *offsets,
+                const float *points_xy, ufm_score *out) {
+    if (n_paths < 1 || !offsets || !points_xy || !out || offsets[0] != 0) return UFM_ERR_INVALID;
+    const int n_shards = (n_maps + per - 1) / per;
+    std::vector<std::vector<ScoreQuery>> q((size_t)n_shards);
+    for (int k = 0; k < n_paths; ++k) {
+        const int i = map_index ? map_index[k] : 0;
+        if (i < 0 || i >= n_maps || offsets[k + 1] < offsets[k]) return UFM_ERR_INVALID;
+        const Engine *e = shards[i / per];
+        if (!e->allocated || !e->maps[i % per].have_map) return UFM_ERR_INVALID;
+        q[i / per].push_back(ScoreQuery{i % per, (size_t)k});
+    }
+    for (int s = 0; s < n_shards; ++s) {
+        if (q[s].empty()) continue;
+        const int rc = engine_score(shards[s], q[s].data(), q[s].size(), offsets, points_xy, out);
+        if (rc != UFM_OK) return rc;
+    }
+    return UFM_OK;
+}
+
+// The device form: every path on map m, offsets, points and records in this device's memory; queued on the engine's stream, nothing
+// copied, nothing waited for (flush_deferred() itself only queues, unless a held patch has to be staged).
+int engine_score_device(Engine *e, int m, int n_paths, int total_points, const int32_t *dev_offsets, const float *dev_points_xy, ufm_score *dev_out) {
+    if (!e || !e->allocated || m < 0 || m >= e->nmaps || !e->maps[m].have_map) return UFM_ERR_INVALID;
+    if (n_paths < 1 || total_points < 0 || !dev_offsets || !dev_points_xy || !dev_out) return UFM_ERR_INVALID;
+    HIPCHK(hipSetDevice(e->device));
+    { int rc = e->flush_deferred(); if (rc != UFM_OK) return rc; }
+    k_score_paths<<<(unsigned)n_paths, 64, 0, e->stream>>>(path_field(e, 0), e->P.cstride, dev_offsets, nullptr, m, dev_points_xy, total_points, dev_out);
+    HIPCHK(hipGetLastError());
     return UFM_OK;
 }
 

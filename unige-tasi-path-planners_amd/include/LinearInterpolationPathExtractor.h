@@ -77,6 +77,25 @@ class LinearInterpolationPathExtractor {
     return out;
   }
 
+  // Not in the reference: what the CALLER's polylines cost on the raster the planner plans on, and whether they are blocked, in one
+  // call of ufm_score_paths (one wavefront per path).  A query, as extract_paths_from(): nothing of the planner or of this object
+  // changes.  One record per path, in their order (include/ufm_score.h); empty, with last_error set, when the call
+  // fails -- an empty list of paths included.
+  std::vector<ufm_score> score_paths(const std::vector<std::vector<Position>> &paths) {
+    std::vector<ufm_score> out;
+    std::vector<int32_t> offsets(paths.size() + 1, 0);
+    std::vector<float> xy;
+    for (size_t k = 0; k < paths.size(); ++k) {
+      for (const Position &pose : paths[k]) { xy.push_back(pose.x); xy.push_back(pose.y); }
+      offsets[k + 1] = static_cast<int32_t>(xy.size() / 2);
+    }
+    if (xy.empty()) xy.resize(2);      // (an address even when no path has a point)
+    std::vector<ufm_score> records(paths.size());
+    last_error = ufm_score_paths(map.native_handle(), static_cast<int>(paths.size()), offsets.data(), xy.data(), records.data());
+    if (last_error == UFM_OK) out.swap(records);
+    return out;
+  }
+
   std::vector<Position> path_{};
   std::vector<float> cost_{};
   float total_cost = 0;

@@ -17,8 +17,22 @@ Twice the worst residual of the ORACLE's trusted values, rounded up to a whole u
 (seeded white-noise maps of 37 x 43, 16 x 16, 17 x 17, 1 x 40 and 3 x 2 cells, thresholds 1.0 and 0.6, every algorithm and level, four
 replans each at levels 1 and 2); the factor covers seeds and sizes not tried.  Measured: Field D* / Shifted Grid 0.919 ulp, MS-DFM
 1.423 ulp (1.131 on the fresh plans).  tests/test_field_reference.py::test_bounds_are_the_measurement recomputes both.  The engine's
-MS-DFM fields are held to DFM_LOCAL_ULP plus the 8 ulp include/ufm.h documents at ufm_check_info (tests/test_gpu_field_reference.py)."""
+MS-DFM fields are held to DFM_LOCAL_ULP plus the 8 ulp include/ufm.h documents at ufm_check_info (tests/test_gpu_field_reference.py).
+
+SCORE_FP64_CHAIN: trajectory scoring (csrc/ufm_score_rect.h) against its float64 restatement (tests/score_reference.py).  A free path's
+cost, cost_before and dist are held to 0.5 ulp32(ref) -- the one narrowing to fp32 -- plus pieces * Cmax * SCORE_FP64_CHAIN * 2^-53 *
+max(M, 1), the fp64 arithmetic in front of it: M the largest coordinate magnitude of the path, Cmax the dearest chargeable byte.  Derived
+from the header, no measurement in it.  The correctly rounded fp64 operations between the fp32 end points and one piece's share of the
+sum, in score_segment(): dx = bx - ax, dy = by - ay, dx * dx, dy * dy, their sum, the square root (6: the segment's length); for each
+of the two cuts that bound the piece k - ax and the division by dx (4); tn - t0 and its product with the length (2); the product with
+the cell's cost and the two additions, into the segment's sum and into the path's (3): 15.  Each is off by at most 2^-53 of a quantity
+that moves the piece's length by no more than the segment's length (t0, tn <= 1), and a segment between coordinates of magnitude M is
+no longer than 2 sqrt(2) M < 3 M: 15 * 3 = 45.  What this form does not cover, stated rather than hidden: the two additions act on
+partial sums, not on one piece, so over a path they contribute up to (pieces + segments) * 2^-53 * ref, which exceeds a piece's share
+above once a path has more than ~30 max(M, 1) pieces; both terms stay eight orders of magnitude below the half ulp32 in front, and can
+only show when the exact sum lies that close to the middle between two fp32 values."""
 FIELD_RTOL = 1e-6
 DFM_RTOL = 2e-6
 NODE_LOCAL_ULP = 2
 DFM_LOCAL_ULP = 3
+SCORE_FP64_CHAIN = 45
