@@ -116,6 +116,9 @@ def lib():
         L.orc_path_move_log.argtypes = [vp, i]
         L.orc_cost_via.restype = f
         L.orc_cost_via.argtypes = [vp, i, i, i, i, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.orc_min_rhs_info_n.argtypes = [vp, i, vp, vp, vp]
+        L.orc_cost_via_n.argtypes = [vp, i, vp, vp, vp, vp]
+        L.orc_set_fd_ablation.argtypes = [i]
         _LIB = L
     return _LIB
 
@@ -234,6 +237,21 @@ class OraclePlanner:
         a, b = C.c_int32(), C.c_int32()
         c = self.L.orc_cost_via(self.h, int(x), int(y), int(bx), int(by), C.byref(a), C.byref(b))
         return float(np.float32(c)), a.value, b.value
+
+    def min_rhs_info_n(self, xy):
+        """orc_min_rhs_info at every element of xy ([n][2]): (values float32 [n], back-pointers int32 [n][2])"""
+        xy = np.ascontiguousarray(xy, np.int32)
+        out, b = np.empty(len(xy), np.float32), np.empty((len(xy), 2), np.int32)
+        self.L.orc_min_rhs_info_n(self.h, len(xy), xy.ctypes.data, out.ctypes.data, b.ctypes.data)
+        return out, b
+
+    def cost_via_n(self, xy, via):
+        """orc_cost_via at every element of xy ([n][2]) through the back-pointer via ([n][2]): (values float32 [n], int32 [n][2])"""
+        xy, via = np.ascontiguousarray(xy, np.int32), np.ascontiguousarray(via, np.int32)
+        assert xy.shape == via.shape
+        out, b = np.empty(len(xy), np.float32), np.empty((len(xy), 2), np.int32)
+        self.L.orc_cost_via_n(self.h, len(xy), xy.ctypes.data, via.ctypes.data, out.ctypes.data, b.ctypes.data)
+        return out, b
 
     def threshold_uchar(self):
         return self.L.orc_threshold_uchar(self.h)

@@ -925,5 +925,13 @@ float orc_cost_via(const orc_t *p, int x, int y, int bx, int by, int32_t *b0, in
     *b0 = a; *b1 = b;
     return c;
 }
+/* The two calls above for n elements at once (tests/operator_cases.py evaluates hundreds of thousands of constructed neighbourhoods):
+ * xy = [n][2] elements (x, y), via = [n][2] the back-pointers (bx, by); out = [n] values, b = [n][2] what the single call leaves in *b0, *b1. */
+void orc_min_rhs_info_n(const orc_t *p, int n, const int32_t *xy, float *out, int32_t *b) {
+    for (int i = 0; i < n; ++i) out[i] = orc_min_rhs_info(p, xy[2 * i], xy[2 * i + 1], &b[2 * i], &b[2 * i + 1]);
+}
+void orc_cost_via_n(const orc_t *p, int n, const int32_t *xy, const int32_t *via, float *out, int32_t *b) {
+    for (int i = 0; i < n; ++i) out[i] = orc_cost_via(p, xy[2 * i], xy[2 * i + 1], via[2 * i], via[2 * i + 1], &b[2 * i], &b[2 * i + 1]);
+}
 /* test hook: overwrite the G field (e.g. with one read back from the engine) */
 void orc_load_g(orc_t *p, const float *g) { memcpy(p->g, g, p->n * sizeof(float)); }

@@ -129,6 +129,9 @@ float orc_min_rhs_info(const orc_t *p, int x, int y, int32_t *b0, int32_t *b1);
 /* cost through a given back-pointer (node planners: node b; DFM: neighbour cell of the level-1 candidate) on the current G field */
 float orc_cost_via(const orc_t *p, int x, int y, int bx, int by, int32_t *b0, int32_t *b1);
 void orc_load_g(orc_t *p, const float *g);
+/* the two above for n elements at once: xy = [n][2] elements, via = [n][2] back-pointers, out = [n], b = [n][2] (b0, b1) */
+void orc_min_rhs_info_n(const orc_t *p, int n, const int32_t *xy, float *out, int32_t *b);
+void orc_cost_via_n(const orc_t *p, int n, const int32_t *xy, const int32_t *via, float *out, int32_t *b);
 
 #ifdef __cplusplus
 }

@@ -19,6 +19,15 @@ replans each at levels 1 and 2); the factor covers seeds and sizes not tried.  M
 1.423 ulp (1.131 on the fresh plans).  tests/test_field_reference.py::test_bounds_are_the_measurement recomputes both.  The engine's
 MS-DFM fields are held to DFM_LOCAL_ULP plus the 8 ulp include/ufm.h documents at ufm_check_info (tests/test_gpu_field_reference.py).
 
+NODE_OPERATOR_ULP / DFM_OPERATOR_ULP: the same criterion on CONSTRUCTED inputs (tests/operator_cases.py) instead of converged fields -- single
+triangles at every turn of their case chain for every pair of cost bytes, 3 x 3 neighbourhoods with random, tied and unreached values.
+By the same rule: twice the ORACLE's worst residual against float64 over the committed cases, rounded up to a whole ulp, and no less than
+the field bound next to it.  Measured (seed 20): node planners 1.493 ulp (Shifted Grid, family T at `f = b sqrt 2`; Field D* 1.296 at
+`f = b`; the neighbourhood families 1.236 at most), MS-DFM 1.830 ulp (family Q, random wide; obstacles 1.547) -> 3 and 4.  Arbitrary inputs
+reach rounding patterns fixed points do not, hence one more ulp than the field bounds.  tests/test_operator_cases.py::
+test_operator_bounds_are_the_measurement recomputes both; tests/test_gpu_operators.py holds the device functions of csrc/ufm_ops.h to them
+(and to the oracle bit for bit).
+
 SCORE_FP64_CHAIN: trajectory scoring (csrc/ufm_score_rect.h) against its float64 restatement (tests/score_reference.py).  A free path's
 cost, cost_before and dist are held to 0.5 ulp32(ref) -- the one narrowing to fp32 -- plus pieces * Cmax * SCORE_FP64_CHAIN * 2^-53 *
 max(M, 1), the fp64 arithmetic in front of it: M the largest coordinate magnitude of the path, Cmax the dearest chargeable byte.  Derived
@@ -35,4 +44,6 @@ FIELD_RTOL = 1e-6
 DFM_RTOL = 2e-6
 NODE_LOCAL_ULP = 2
 DFM_LOCAL_ULP = 3
+NODE_OPERATOR_ULP = 3
+DFM_OPERATOR_ULP = 4
 SCORE_FP64_CHAIN = 45
