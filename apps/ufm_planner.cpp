@@ -12,13 +12,16 @@
 // LinearInterpolationPathExtractor, reset / set_* / patch_map / step / extract_path, u_time,
 // p_time, e_time, map.size(), map.buckets.
 //
-//   ufm_planner [--planner FD|SG|DFM] [--level K] [--max-moves N] [--verify-follow] [--inflate D] [--auto-heuristic] [--sense R] [--image K P] [--layers N] <fifo_in> <fifo_out>
+//   ufm_planner [--planner FD|SG|DFM] [--level K] [--max-moves N] [--verify-follow] [--inflate D] [--margin OUTER STEP] [--auto-heuristic] [--sense R] [--image K P] [--layers N] <fifo_in> <fifo_out>
 //        start, goal and the `tof` flag arrive in-band after the map (DFM/main.cpp:62-67)
 //   ufm_planner [...] <mapfile> <from_x> <from_y> <to_x> <to_y> <cspace> <fifo_in> <fifo_out> <gui> <tof> <outpath>
 //        the 11-argument form of FDSTAR/main.cpp:16-31 and SGDFM/main.cpp
 // --inflate D: the map and the patches on the wire are RAW and the engine plans on their dilation by the disc of diameter D
 // (ufm_set_cspace; x^2 + y^2 <= (D / 2)^2 on a (2 (D / 2) + 1)-cell square, the footprint of the Python harness' dilate) -- the simulator
 // then need not inflate anything.  The positional <cspace> stays as inert as it is in the reference drivers.
+// --margin OUTER STEP: a soft margin around the disc of --inflate D (without --inflate: D = 1): the footprint is the cone
+// ufm_cspace_cone(D, OUTER, STEP) -- the disc at full cost, then STEP less per cell of distance out to the diameter OUTER
+// (ufm_set_cspace_graded, include/ufm_cspace_graded.h).  The wire carries RAW data as with --inflate.
 // --auto-heuristic: the heuristic multiplier is the smallest cost of the planning raster as the engine holds it (the cost census,
 // ufm_track_costs + "auto_multiplier"); the wire's min_cost is read, as the protocol demands, and not used -- with --inflate the simulator
 // then need not know the inflated map at all.
@@ -95,6 +98,8 @@ struct Options {
   bool tof = false;
   bool verify_follow = false;
   int inflate = 0;           // --inflate D: footprint diameter (<= 1: off)
+  int margin_outer = 0;      // --margin OUTER STEP: the cone around that disc out to the diameter OUTER (0: off) ...
+  int margin_step = 0;       // ... losing STEP per cell
   bool auto_heuristic = false;   // --auto-heuristic: the multiplier follows the engine's planning raster
   int sense = -1;            // --sense R: radius of the field of view the planner uncovers itself (< 0: off)
   int image = 0;             // --image K P: the wire carries the bitmap, blurred here with K Gaussian taps (0: off) ...
@@ -145,7 +150,13 @@ int serve(Options opt, bool cell_planner, bool indirect) {
   planner.set_occupancy_threshold(1);
   planner.set_heuristic_multiplier((float)min_cost);
   if (opt.auto_heuristic) planner.set_auto_heuristic(true);
-  if (opt.inflate > 1) {
+  if (opt.margin_outer > 0) {
+    std::vector<uint8_t> cone((size_t)31 * 31);
+    if (ufm_cspace_cone(std::max(opt.inflate, 1), opt.margin_outer, opt.margin_step, cone.data()) != UFM_OK)
+      throw std::runtime_error("--margin: D <= OUTER <= 31, at most 15 rings, STEP is 1 .. 254");
+    const int n = 2 * (opt.margin_outer / 2) + 1;
+    planner.set_cspace_graded(cone.data(), n, n);
+  } else if (opt.inflate > 1) {
     const int r = opt.inflate / 2, n = 2 * r + 1;
     if (n > 31) throw std::runtime_error("--inflate: the footprint is at most 31 cells wide");
     std::vector<uint8_t> disc((size_t)n * n);
@@ -268,7 +279,7 @@ int serve(Options opt, bool cell_planner, bool indirect) {
 
 void usage(const char *argv0) {
   std::fprintf(stderr,
-               "Usage:\n\t%s [--planner FD|SG|DFM] [--level K] [--max-moves N] [--verify-follow] [--inflate D] [--auto-heuristic] [--sense R] [--image K P] [--layers N] <fifo_in> <fifo_out>\n"
+               "Usage:\n\t%s [--planner FD|SG|DFM] [--level K] [--max-moves N] [--verify-follow] [--inflate D] [--margin OUTER STEP] [--auto-heuristic] [--sense R] [--image K P] [--layers N] <fifo_in> <fifo_out>\n"
                "\t%s [...] <mapfile> <from_x> <from_y> <to_x> <to_y> <cspace> <fifo_in> <fifo_out> <gui> <tof> <outpath>\n",
                argv0, argv0);
 }
@@ -299,6 +310,7 @@ int main(int argc, char **argv) {
     else if (a == "--max-moves" && i + 1 < argc) opt.max_moves = std::atol(argv[++i]);
     else if (a == "--verify-follow") opt.verify_follow = true;
     else if (a == "--inflate" && i + 1 < argc) opt.inflate = std::atoi(argv[++i]);
+    else if (a == "--margin" && i + 2 < argc) { opt.margin_outer = std::atoi(argv[++i]); opt.margin_step = std::atoi(argv[++i]); }
     else if (a == "--auto-heuristic") opt.auto_heuristic = true;
     else if (a == "--sense" && i + 1 < argc) opt.sense = std::atoi(argv[++i]);
     else if (a == "--image" && i + 2 < argc) { opt.image = std::atoi(argv[++i]); opt.image_penalty = std::atoi(argv[++i]); }

@@ -515,6 +515,9 @@ int ufm_batch_extract_paths_from(ufm_batch_t *b, int n_starts, const int32_t *ma
  * calls of a planner and the two of a batch.  The contract and the declarations are a header of their own, included here: whoever
  * includes ufm.h has them. ---- */
 #include "ufm_score.h"
+/* ---- graded footprint: ufm_set_cspace with a drop per cell, a margin around obstacles that decays with distance.  As above: a header
+ * of its own, included here. ---- */
+#include "ufm_cspace_graded.h"
 
 #ifdef __cplusplus
 }

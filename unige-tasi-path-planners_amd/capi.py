@@ -126,6 +126,11 @@ _SCORE_OPS = [
     ("score_paths_device", "pB", [_i, _i, _vp, _vp, _vp]),
 ]
 SCORE_SYMBOLS = [_FORMS[form][0] + op for op, forms, _ in _SCORE_OPS for form in forms]
+# The graded footprint, likewise: include/ufm_cspace_graded.h, GRADED_SYMBOLS (checked by tests/test_cspace_graded_surface.py); the
+# same debt.
+_GRADED_OPS = [("set_cspace_graded", "pb", _MASK), ("cspace_cone", "f", [_i, _i, _i, _vp])]
+GRADED_SYMBOLS = [_FORMS[form][0] + op for op, forms, _ in _GRADED_OPS for form in forms]
+CSPACE_OUTSIDE, CSPACE_MAX_LEVELS = 255, 16     # UFM_CSPACE_OUTSIDE, UFM_CSPACE_MAX_LEVELS
 
 _LIB_PATH = os.path.join(_HERE, "libufm.so")
 
@@ -158,7 +163,7 @@ def load_library():
                        "or __graft_entry__.build()); there is no CPU fallback")
     L = C.CDLL(so)
     fn = {kind: types.SimpleNamespace() for kind in "pbf"}
-    for op, forms, args in _OPS + _SCORE_OPS:
+    for op, forms, args in _OPS + _SCORE_OPS + _GRADED_OPS:
         for form in forms:
             prefix, head = _FORMS[form]
             func = getattr(L, prefix + op)
@@ -197,6 +202,18 @@ def _cspace_args(mask, anchor):
         raise UfmError("a footprint is a matrix")
     ar, ac = (-1, -1) if anchor is None else (int(anchor[0]), int(anchor[1]))
     return mask, mask.shape[1], mask.shape[0], ar, ac
+
+
+def cspace_cone(inner_d, outer_d, step):
+    """ufm_cspace_cone: the cone footprint as ufm_set_cspace_graded takes it -- drop 0 on the disc of diameter inner_d, then `step` more
+    per ring of one cell out to the disc of diameter outer_d (at most 254), 255 beyond; a uint8 matrix of edge 2 * (outer_d // 2) + 1
+    with the anchor at its centre.  The C definition, called, not restated."""
+    r = int(outer_d) // 2
+    fits = 0 <= r <= 15                        # (otherwise the call is made without a buffer, for its error)
+    drop = np.zeros((2 * r + 1, 2 * r + 1) if fits else (1, 1), np.uint8)
+    load_library()
+    _call(_FN["f"].cspace_cone, int(inner_d), int(outer_d), int(step), drop.ctypes.data if fits else None)
+    return drop
 
 
 def sensor_disc(radius):
@@ -309,6 +326,13 @@ class _Handle:
         for every map on every shard"""
         mask, mw, mh, ar, ac = _cspace_args(mask, anchor)
         _call(self._F.set_cspace, self.h, mask.ctypes.data, mw, mh, ar, ac)
+
+    def set_cspace_graded(self, drop, anchor=None):
+        """ufm_set_cspace_graded: a footprint with a drop per cell (uint8 matrix, 255 = outside; drop[anchor] == 0; at most 16 distinct
+        values): planning = max over the footprint of max(raw - drop, 0).  cspace_cone(inner_d, outer_d, step) makes the usual one.
+        Before the first set_map, as set_cspace, which it replaces and is replaced by.  A batch: for every map on every shard"""
+        drop, mw, mh, ar, ac = _cspace_args(drop, anchor)
+        _call(self._F.set_cspace_graded, self.h, drop.ctypes.data, mw, mh, ar, ac)
 
     def set_sensor(self, mask, anchor=None):
         """ufm_set_sensor: the field of view (uint8 matrix, non-zero = seen; anchor (row, col), None: the centre); sensor_disc(r) is the

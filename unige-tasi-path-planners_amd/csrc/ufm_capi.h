@@ -211,6 +211,15 @@ int ufm_batch_set_cspace(ufm_batch_t *b, const uint8_t *mask, int mw, int mh, in
     return UFM_OK;
 }
 int ufm_set_cspace(ufm_t *p, const uint8_t *mask, int mw, int mh, int anchor_row, int anchor_col) { return ufm_batch_set_cspace(p, mask, mw, mh, anchor_row, anchor_col); }
+// (include/ufm_cspace_graded.h)
+int ufm_batch_set_cspace_graded(ufm_batch_t *b, const uint8_t *drop, int mw, int mh, int anchor_row, int anchor_col) {
+    if (!b || b->shards.empty() || !cspace_graded_valid(drop, mw, mh, anchor_row, anchor_col)) return UFM_ERR_INVALID;
+    for (Engine *e : b->shards) for (const MapState &ms : e->maps) if (ms.have_map) return UFM_ERR_INVALID;
+    for (Engine *e : b->shards) { const int rc = engine_set_cspace_graded(e, drop, mw, mh, anchor_row, anchor_col); if (rc != UFM_OK) return rc; }
+    return UFM_OK;
+}
+int ufm_set_cspace_graded(ufm_t *p, const uint8_t *drop, int mw, int mh, int anchor_row, int anchor_col) { return ufm_batch_set_cspace_graded(p, drop, mw, mh, anchor_row, anchor_col); }
+int ufm_cspace_cone(int inner_d, int outer_d, int step, uint8_t *drop) { return cspace_cone(inner_d, outer_d, step, drop) ? UFM_OK : UFM_ERR_INVALID; }
 int ufm_batch_set_sensor(ufm_batch_t *b, const uint8_t *mask, int mw, int mh, int anchor_row, int anchor_col) {
     if (!b || b->shards.empty() || !sensor_valid(mask, mw, mh, anchor_row, anchor_col)) return UFM_ERR_INVALID;
     for (Engine *e : b->shards) { const int rc = engine_set_sensor(e, mask, mw, mh, anchor_row, anchor_col); if (rc != UFM_OK) return rc; }

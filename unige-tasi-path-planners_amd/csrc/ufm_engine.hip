@@ -50,6 +50,7 @@ namespace {
 
 #include "ufm_region.h"
 #include "ufm_cspace.h"
+#include "ufm_cspace_graded.h"
 #include "ufm_census.h"
 #include "ufm_sensor.h"
 #include "ufm_prepare.h"

@@ -246,7 +246,8 @@ struct Engine : Knobs {     // the tuning members -- what ufm_set_param sets -- 
     // or runs.  On: d_raw holds the caller's raster per map, P.cost its dilation by the footprint; a raw patch goes to d_raw, the rectangle
     // of P.cost it can change is dilated into d_cs_patch and that one is applied as an ordinary patch.
     CspaceMask cs;
-    DevArray<uint8_t> d_raw;         // [nmaps][L][W]; dropped with the rasters (release())
+    CspaceLevels csl;                // ufm_set_cspace_graded (ufm_cspace_graded.h, section 4.16): cs is then the support; n <= 1: a flat footprint
+    DevArray<uint8_t> d_raw;        // [nmaps][L][W]; dropped with the rasters (release())
     ScratchBytes d_cs_patch;           // the dilated grown rectangle of the patch being applied, dense
     void cspace_dilate(int m, uint8_t *out, int pitch, const PatchRect &r);
     // Cost census (ufm_track_costs; ufm_census.h).  Off -- the default -- nothing below exists or runs.  On: d_census

@@ -135,7 +135,20 @@ int engine_patch(Engine *e, int m, const uint8_t *src, bool on_device, int x, in
 }
 
 // ---- C-space inflation: planning raster == dilate(raw raster), kept at a cost proportional to the patch ----
+// (the one place that knows which kind of footprint is set: everything else works on the support, cs)
 void Engine::cspace_dilate(int m, uint8_t *out, int pitch, const PatchRect &r) {
+    if (csl.n > 1) {
+        CspaceGradedJob j{};
+        j.raw = d_raw + (size_t)m * P.cstride; j.out = out;
+        j.L = L; j.W = W; j.x0 = r.x; j.y0 = r.y; j.h = r.h; j.w = r.w; j.pitch = pitch;
+        j.mh = cs.mh; j.mw = cs.mw; j.ar = cs.ar; j.ac = cs.ac; j.nl = csl.n;
+        for (int l = 0; l < csl.n; ++l) {
+            j.drop[l] = csl.drop[l];
+            for (int a = 0; a < CSPACE_MAX; ++a) j.rows[l][a] = csl.rows[l][a];
+        }
+        k_cspace_dilate_graded<<<dim3((r.w + CS_TC - 1) / CS_TC, (r.h + CS_TR - 1) / CS_TR), 256, 0, stream>>>(j);
+        return;
+    }
     CspaceJob j{};
     j.raw = d_raw + (size_t)m * P.cstride; j.out = out;
     j.L = L; j.W = W; j.x0 = r.x; j.y0 = r.y; j.h = r.h; j.w = r.w; j.pitch = pitch;
@@ -148,7 +161,21 @@ int engine_set_cspace(Engine *e, const uint8_t *mask, int mw, int mh, int ar, in
     if (!e) return UFM_ERR_INVALID;
     for (const MapState &ms : e->maps) if (ms.have_map) return UFM_ERR_INVALID;
     if (!cspace_pack(mask, mw, mh, ar, ac, &e->cs)) return UFM_ERR_INVALID;
+    e->csl = CspaceLevels{};     // (the last footprint call before the first raster wins: a graded one is replaced)
     // (arrays without a map -- a ufm_set_map that failed after its allocation -- were sized without the raw store: the next one allocates anew)
+    if (e->allocated) { HIPCHK(hipSetDevice(e->device)); e->release(); }
+    return UFM_OK;
+}
+// ufm_set_cspace_graded / ufm_batch_set_cspace_graded: the same property, with a drop per cell.  The support goes where the flat mask
+// goes; drops that are all 0 leave one level and the state ufm_set_cspace would leave for the mask drop != 255 -- the flat kernel runs.
+int engine_set_cspace_graded(Engine *e, const uint8_t *drop, int mw, int mh, int ar, int ac) {
+    if (!e) return UFM_ERR_INVALID;
+    for (const MapState &ms : e->maps) if (ms.have_map) return UFM_ERR_INVALID;
+    CspaceMask support;
+    CspaceLevels levels;
+    if (!cspace_graded_pack(drop, mw, mh, ar, ac, &support, &levels)) return UFM_ERR_INVALID;
+    e->cs = support;
+    e->csl = levels.n > 1 ? levels : CspaceLevels{};
     if (e->allocated) { HIPCHK(hipSetDevice(e->device)); e->release(); }
     return UFM_OK;
 }

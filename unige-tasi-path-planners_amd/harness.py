@@ -92,6 +92,24 @@ def dilate(img, diameter):
     return out
 
 
+def dilate_graded(img, drop, anchor=None):
+    """grey-scale dilation by a graded footprint (include/ufm_cspace_graded.h): drop[mh][mw] uint8, 255 = outside, anchor (row, col),
+    None: the centre; out[i][j] = max over the footprint of max(img[i + a - ar][j + b - ac] - drop[a][b], 0), cells outside the image
+    ignored (they are padded with 0, which no drop lifts above 0)"""
+    drop = np.asarray(drop, np.uint8)
+    mh, mw = drop.shape
+    ar, ac = (mh // 2, mw // 2) if anchor is None else anchor
+    L, W = img.shape
+    p = np.zeros((L + mh - 1, W + mw - 1), np.int16)
+    p[ar:ar + L, ac:ac + W] = img
+    out = np.zeros((L, W), np.int16)
+    for a in range(mh):
+        for b in range(mw):
+            if drop[a, b] != 255:
+                out = np.maximum(out, p[a:a + L, b:b + W] - np.int16(drop[a, b]))
+    return out.astype(np.uint8)
+
+
 def round_patch_update(data_l, data_h, center, radius):
     """Reveal the high-resolution data inside the disc around center = (col, row); returns
     (new low-resolution map, (top, left), (row slice, col slice)) -- the rectangle that bounds the
@@ -167,7 +185,7 @@ class Pipes:
 def run_mission(cmd, pipe_to_planner, pipe_from_planner, img_h, start, goal, radius=5, cspace_diameter=1,
                 low_res_penalty=10, use_heuristic=False, max_moves=10000, on_map=None, on_move=None, display_shift=0.0,
                 append_pipes=True, tof=False, on_expanded=None, planner_inflates=False, planner_min_cost=False, planner_senses=False,
-                planner_prepares=False, filter_size=3, layers=None, planner_layers=False):
+                planner_prepares=False, filter_size=3, layers=None, planner_layers=False, margin=None):
     """One mission as Tests/run_test.py:85-177 runs it: launch the planner process `cmd`, send the
     C-space of the low-resolution map, then per robot position reveal the disc of radius `radius`,
     send its bounding patch and the heuristic hint, receive the planned path.  start / goal are
@@ -195,13 +213,22 @@ def run_mission(cmd, pipe_to_planner, pipe_from_planner, img_h, start, goal, rad
     happens here and the COMPOSED patches are shipped, as the reference does.
     planner_layers: the planner process keeps the layers itself (ufm_planner --layers N with N = 1 + len(layers); needs planner_senses):
     the extra high-resolution rasters go out ONCE, behind the survey (or behind the bitmap with planner_prepares), positions thereafter.
+    margin: (outer, step) -- a soft margin around the C-space disc: wherever this function or the planner would dilate by the disc of
+    cspace_diameter, it is by the cone ufm_cspace_cone(max(cspace_diameter, 1), outer, step) instead (dilate_graded here; with
+    planner_inflates the planner's own, ufm_planner --inflate D --margin OUTER STEP, which the caller puts into cmd).
     Returns the list of positions visited and whether the planner reported the end."""
+    if margin is not None:
+        from .capi import cspace_cone          # (the one definition of the cone is the library's)
+        cone = cspace_cone(max(cspace_diameter, 1), margin[0], margin[1])
+        inflate = lambda raw: dilate_graded(raw, cone)
+    else:
+        inflate = lambda raw: dilate(raw, cspace_diameter)
     layers = [np.ascontiguousarray(a, dtype=np.uint8) for a in (layers or [])]
     if planner_layers and not planner_senses:
         raise ValueError("planner_layers: the planner uncovers the layers itself, so it must sense too (planner_senses)")
     if any(a.shape != np.shape(img_h) for a in layers):
         raise ValueError("layers: every raster has the bitmap's shape")
-    if planner_prepares and cspace_diameter > 1 and not planner_inflates:
+    if planner_prepares and (cspace_diameter > 1 or margin is not None) and not planner_inflates:
         raise ValueError("planner_prepares: the planner makes the raw map, so it must inflate it too (planner_inflates)")
     for p in (pipe_to_planner, pipe_from_planner):
         if not os.path.exists(p):
@@ -217,7 +244,7 @@ def run_mission(cmd, pipe_to_planner, pipe_from_planner, img_h, start, goal, rad
         io.send("b", 0)
         data_l, data_h = simulation_data(img_h, low_res_penalty, filter_size)
         host_inflates = not (planner_inflates and planner_min_cost)
-        cspace = dilate(data_l, cspace_diameter) if host_inflates else data_l
+        cspace = inflate(data_l) if host_inflates else data_l
         min_cost = int(data_l.min()) if planner_min_cost else int(cspace.min())
         height, width = cspace.shape
         io.send("ii", width, height)
@@ -254,7 +281,7 @@ def run_mission(cmd, pipe_to_planner, pipe_from_planner, img_h, start, goal, rad
             data_l, (top, left), ranges = round_patch_update(data_l, data_h, center, radius)
             known = [round_patch_update(k, a, center, radius)[0] for k, a in zip(known, layers)]      # run_test.py:136-139: the same disc in every layer
             raw = np.maximum.reduce([data_l] + known)                                                # :140
-            cspace = dilate(raw, cspace_diameter) if host_inflates else raw
+            cspace = inflate(raw) if host_inflates else raw
             patch = np.ascontiguousarray((raw if planner_inflates else cspace)[ranges[0], ranges[1]])
             if use_heuristic:
                 min_cost = int(raw.min()) if planner_min_cost else int(cspace.min())

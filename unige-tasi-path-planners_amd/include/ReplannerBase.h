@@ -70,6 +70,10 @@ class ReplannerBase {
   void set_cspace(const uint8_t *mask, int mw, int mh, int anchor_row = -1, int anchor_col = -1) {
     check(ufm_set_cspace(handle_, mask, mw, mh, anchor_row, anchor_col));
   }
+  /** The same with a drop per cell (ufm_set_cspace_graded, include/ufm_cspace_graded.h): drop[mh][mw], 255 = outside, drop[anchor] == 0. */
+  void set_cspace_graded(const uint8_t *drop, int mw, int mh, int anchor_row = -1, int anchor_col = -1) {
+    check(ufm_set_cspace_graded(handle_, drop, mw, mh, anchor_row, anchor_col));
+  }
   /** Sensor reveal on the device (ufm_set_sensor / ufm_set_survey / ufm_reveal; no reference counterpart: the reference's simulator keeps
    *  the high-resolution raster and ships the revealed rectangle every move, run_simulator.py:9-28,177): the field of view mask[mh][mw]
    *  with its anchor (-1, -1: the centre), the survey raster -- what the sensor would see, of the map's size, after set_map --, and
